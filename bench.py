@@ -3,6 +3,9 @@
 
 Contract (see DESIGN.md "Measurement"):
   python bench.py --gpus N --steps K --warmup W           (N>1 under torch.distributed.run)
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds what takes
+runs of its own or more than the timed window: the measured HBM stream copy and the roofline blocks
+that divide by it, and the CPU baseline.  --dump-outputs DIR saves the last timed step's outputs.
 A "step" is one tick of every env of the batch: the step kernel with same-step in-kernel auto-reset,
 reading that tick's actions (synthetic uniform policy, 1 B/env, generated on the device before the
 timed region) from HBM.  Inputs and state are resident in HBM for the whole timed region.
@@ -175,6 +178,44 @@ def load_latency(workload: str, n_envs: int, avg_kernel_s: float):
             "phases_mean_cycles": d.get("phases_mean_cycles"), "source": p}
 
 
+def ensure_built() -> None:
+    """Build the in-tree library if it is missing or older than its sources (file-locked across
+    ranks).  A current library is left alone, lock file included, so that the benchmark also runs
+    from a tree that its user cannot write to."""
+    from pgtg_amd.build import build, needs_build
+    if needs_build():
+        build()
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # of the files of one --dump-outputs run, over all ranks
+
+
+def dump_outputs(path: str, arrays: dict, n_envs: int, env_offset: int = 0, rank: int = 0, world: int = 1,
+                 valid=None) -> None:
+    """--dump-outputs: save per-env arrays (name -> [n_envs, ...] device tensor or numpy array, or
+    None) as <path>/<name>.npy (<name>.rank<r>.npy for a sharded run): float64 for float64 inputs,
+    float32 otherwise.  A batch over the byte budget is cut to a fixed sample of envs (seeded
+    choice, sorted; the same for every run of the same arguments), whose global indices are saved
+    as env_index.npy.  `valid` ([n_envs] bool): the final_* arrays hold a row only where it is set,
+    zeros elsewhere."""
+    import numpy as np
+    import torch
+
+    arrays = {k: torch.as_tensor(v) for k, v in arrays.items() if v is not None}
+    per_env = 8 + sum(v[0].numel() * (8 if v.dtype == torch.float64 else 4) for v in arrays.values())
+    m = max(1, min(n_envs, DUMP_BUDGET_BYTES // world // per_env))
+    idx = np.arange(n_envs) if m == n_envs else np.sort(np.random.default_rng(0xD0).choice(n_envs, m, replace=False))
+    os.makedirs(path, exist_ok=True)
+    sfx = ".npy" if world == 1 else f".rank{rank}.npy"
+    np.save(os.path.join(path, "env_index" + sfx), (idx + env_offset).astype(np.float64))
+    for k, v in arrays.items():
+        rows = v[torch.as_tensor(idx, device=v.device)]
+        if valid is not None and k.startswith("final_"):
+            rows = rows * valid[torch.as_tensor(idx, device=valid.device)].view(-1, *[1] * (rows.dim() - 1))
+        rows = rows.cpu().numpy()
+        np.save(os.path.join(path, k + sfx), rows.astype(np.float64 if rows.dtype == np.float64 else np.float32))
+
+
 def adapter_bench(args) -> None:
     """The reference caller's interface (pgtg/train.py:39-55: TimeLimit(100) -> FlattenObservation ->
     SubprocVecEnv) served by PGTGSB3VecEnv: K steps of step_async/step_wait with the flattened
@@ -184,8 +225,7 @@ def adapter_bench(args) -> None:
     import numpy as np
     import torch
 
-    from pgtg_amd.build import build
-    build()
+    ensure_built()
     from pgtg_amd.sb3 import PGTGSB3VecEnv
     _, desc, n, kwargs = WORKLOADS["train"]
     n = args.envs or n
@@ -220,6 +260,8 @@ def adapter_bench(args) -> None:
                 done += 1
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and args.steps:  # what the last step_wait returned
+        dump_outputs(args.dump_outputs, {"obs": obs, "rewards": rew, "dones": dones}, n)
     rec = {"metric": "env-steps/sec through the SB3 VecEnv adapter (PGTGSB3VecEnv.step_async/step_wait)",
            "value": n * args.steps / dt, "unit": "env-steps/s", "n_gpus": 1, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
@@ -243,7 +285,14 @@ def main():
     # on, split over the N GPUs.  cfg2/cfg4/cfg3 = configs[1]/[3]/[2] (single-GPU configs).
     ap.add_argument("--workload", default="cfg5", choices=sorted(WORKLOADS))
     ap.add_argument("--envs", type=int, default=0, help="override the batch (envs over all GPUs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the HBM stream copy and report the roofline blocks, and time the CPU "
+                         "baseline (single-GPU runs); a plain run only sets up, warms up and times the steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, save the outputs of the last timed step (observations, rewards, "
+                         "flags, terminal observations of the envs that finished in it) as DIR/<name>.npy, "
+                         "float32/float64, a fixed sample of the envs when the batch is too large")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--dist", action="store_true",
                     help="initialise the process group and run the counter all-reduce on the device even "
@@ -283,8 +332,7 @@ def main():
     dev = torch.device("cuda", local)
     red_dev = dev if backend == "nccl" else None
 
-    from pgtg_amd.build import build
-    build()  # no-op when the in-tree library is current (file-locked across ranks)
+    ensure_built()
     from pgtg_amd.config import make_spec
     from pgtg_amd.dist import Shard, reduce_counters, reduce_sum
     from pgtg_amd.vector import PGTGVecEnv
@@ -299,7 +347,7 @@ def main():
     max_steps = kwargs.pop("max_episode_steps", None)
     spec = make_spec(**kwargs)
     shard = Shard(rank, world, n_local)
-    peak_copy = measure_hbm(local) if rank == 0 else 0.0
+    peak_copy = measure_hbm(local) if rank == 0 and args.full else 0.0
     tune = {k: v for k, v in (("envs_per_block", args.envs_per_block), ("kt_wpc", args.kt_wpc),
                               ("kt_cap", args.kt_cap), ("queue_mode", args.queue_mode)) if v} or None
     env = PGTGVecEnv(n_local, spec=spec, device=local, autoreset=True, max_episode_steps=max_steps, tune=tune)
@@ -335,6 +383,16 @@ def main():
     window_ms = ev0.elapsed_time(ev1)
     steps1, eps1 = env.counters()
     maps1 = env.queue_maps()
+    if args.dump_outputs and args.steps:
+        # the handle's output tensors after the last timed step (step()'s return values); the terminal
+        # observations count only for the envs that finished in that step, the other rows are zeroed
+        dump_outputs(args.dump_outputs,
+                     {"obs_map": env.obs_map, "position": env.position, "velocity": env.velocity,
+                      "next_subgoal_direction": env.nsd, "reward": env.reward, "cost": env.cost,
+                      "terminated": env.terminated, "truncated": env.truncated, "braking": env.braking,
+                      "final_obs_map": env.final_map, "final_position": env.final_position,
+                      "final_velocity": env.final_velocity, "final_next_subgoal_direction": env.final_nsd},
+                     n_local, shard.offset, rank, world, valid=env.terminated | env.truncated)
     # the step kernel's average launch duration for the roofline: the event pair around the timed
     # window divided by the launches (back-to-back launches on one stream: the window is their device
     # time; it agrees with rocprofv3's per-kernel average to < 0.5 %, profiles/r04/f2, while brackets
@@ -363,14 +421,7 @@ def main():
         np.savez(f"{args.digest}.rank{rank}.npz", digest=d, offset=shard.offset, world=world,
                  steps=t_end, workload=args.workload)
 
-    if rank == 0:
-        resets_per_launch = (eps1 - eps0) / max(1, args.steps)
-        avg_kernel_s = (kern_ms / max(1, launches)) / 1e3
-        cars = env.mean_cars() if spec.traffic_density > 0 else 0.0
-        alg = algorithmic_bytes(spec, n_local, resets_per_launch, cars)
-        achieved = alg / avg_kernel_s / 1e9 if avg_kernel_s > 0 else 0.0
-        peak = max(peak_copy, PEAK_HBM_GUIDE_GBS)  # the higher of the two measured copy rates
-        traffic, traffic_src = load_traffic(args.workload, n_local)
+    if rank == 0:  # the headline line
         rec = {
             "metric": METRIC, "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": 1e3 * t_max / args.steps, "higher_is_better": True,
@@ -384,6 +435,16 @@ def main():
             # k_envq: maps its helper waves generated in the window for later episodes (the rings start
             # full: reset fills them, k_qfill), beside the episodes that took a queued map
             "queue_maps_generated": total_maps if maps1 else None,
+        }
+    if rank == 0 and args.full:  # the roofline blocks (the measured stream copy) and the CPU baseline
+        resets_per_launch = (eps1 - eps0) / max(1, args.steps)
+        avg_kernel_s = (kern_ms / max(1, launches)) / 1e3
+        cars = env.mean_cars() if spec.traffic_density > 0 else 0.0
+        alg = algorithmic_bytes(spec, n_local, resets_per_launch, cars)
+        achieved = alg / avg_kernel_s / 1e9 if avg_kernel_s > 0 else 0.0
+        peak = max(peak_copy, PEAK_HBM_GUIDE_GBS)  # the higher of the two measured copy rates
+        traffic, traffic_src = load_traffic(args.workload, n_local)
+        rec.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s",
                          "frac": achieved / peak if peak > 0 else None, "traffic": traffic,
                          "traffic_source": traffic_src,
@@ -402,7 +463,7 @@ def main():
                          "resets_per_launch": resets_per_launch, "cars_per_env": cars,
                          "envs_per_workgroup": env.launch_info()[0], "lds_bytes": env.launch_info()[1],
                          "workgroups_per_cu": env.occupancy()},
-        }
+        })
         issue = load_issue(args.workload, n_local, avg_kernel_s)
         if issue is not None:
             rec["roofline_issue"] = issue
@@ -411,6 +472,7 @@ def main():
             rec["roofline_latency"] = lat
         if world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(spec, args.cpu_seconds)
+    if rank == 0:
         print(json.dumps(rec), flush=True)
     env.close()
     if use_dist:

@@ -38,7 +38,7 @@ for rep in $(seq $R); do
 import csv
 print('$W $V', '  '.join(f\"{r['Name'][:18]} {float(r['AverageNs'])/1e3:.1f}us\" for r in csv.DictReader(open('$f')) if 'k_env' in r['Name'] or 'k_traffic' in r['Name']))"
       else
-        timeout -k 10 180 python bench.py --workload $W --steps ${AB_STEPS:-100} --warmup ${AB_WARMUP:-20} --no-cpu-baseline "${ARGS[@]}" > $O/abm.json 2> $O/abm.err || { tail -5 $O/abm.err; exit 1; }
+        timeout -k 10 180 python bench.py --full --workload $W --steps ${AB_STEPS:-100} --warmup ${AB_WARMUP:-20} --no-cpu-baseline "${ARGS[@]}" > $O/abm.json 2> $O/abm.err || { tail -5 $O/abm.err; exit 1; }
         python -c "import json; d=json.load(open('$O/abm.json')); r=d['roofline']; print('$W $V', f\"{d['value']/1e6:.2f}M\", f\"kern {r['avg_kernel_us']:.1f}us\")"
       fi
     ) || exit 1

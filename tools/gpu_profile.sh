@@ -15,11 +15,11 @@ mkdir -p gpurun_out/prof_$TAG
 python -c "from pgtg_amd.build import build; build()" || exit 1
 for W in $WLS; do
   D=gpurun_out/prof_$TAG/$W
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $D/trace -o run --output-format csv -- python bench.py --workload $W --steps 1000 --warmup 50 --no-cpu-baseline > $D.trace.json
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $D/trace -o run --output-format csv -- python bench.py --full --workload $W --steps 1000 --warmup 50 --no-cpu-baseline > $D.trace.json
   timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $D/fetch -o run --output-format csv -- python bench.py --workload $W --steps 60 --warmup 200 --no-cpu-baseline > /dev/null
   timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d $D/write -o run --output-format csv -- python bench.py --workload $W --steps 60 --warmup 200 --no-cpu-baseline > /dev/null
   python tools/pmc.py $W $D/fetch $D/write $TAG > $D.pmc.json
   cp profiles/pmc_$W.json $D.pmc_profile.json
-  timeout -k 10 300 python bench.py --workload $W --no-cpu-baseline > $D.bench.json
+  timeout -k 10 300 python bench.py --full --workload $W --no-cpu-baseline > $D.bench.json
   echo "$W done"
 done

@@ -4,11 +4,11 @@
 #   tests            pytest -m gpu (whole suite)
 #   tests:<expr>     pytest -m gpu -k <expr>
 #   smoke            __graft_entry__.smoke()
-#   bench            the default bench line (configs[4], with the CPU baseline)
+#   bench            the default bench line with --full (configs[4], roofline blocks and the CPU baseline)
 #   driver           the driver's own line: bench.py --gpus 1 --steps 20 --warmup 5
 #   ramp:<wl>        per-launch kernel time of the first 80 launches after a reset (tools/ramp.py)
-#   bench:<wl>       bench.py --workload <wl> --steps 200 --warmup 20
-#   benchlong:<wl>   bench.py --workload <wl> with the default 1000-step window
+#   bench:<wl>       bench.py --full --workload <wl> --steps 200 --warmup 20
+#   benchlong:<wl>   bench.py --full --workload <wl> with the default 1000-step window
 #   rccl             bench.py under torch.distributed.run, one rank, nccl backend, --dist (RCCL init +
 #                    the device counter all-reduce), 131 072 envs
 #   ranks            2, 4 and 8 ranks on one GPU (gloo) at the full configs[4] batch (8 ranks: the 131 072-env
@@ -49,7 +49,7 @@ for S in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
       tail -2 $O/smoke.log ;;
     bench)
-      timeout -k 10 400 python -u bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
+      timeout -k 10 400 python -u bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
       cat $O/bench_default.json ;;
     driver)
       timeout -k 10 400 python -u bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err || { tail -20 $O/bench_driver.err; exit 1; }
@@ -59,15 +59,15 @@ for S in "$@"; do
       tail -6 $O/ramp_${S#ramp:}.log ;;
     benchlong:*)
       W=${S#benchlong:}
-      timeout -k 10 400 python -u bench.py --workload $W --no-cpu-baseline > $O/benchlong_$W.json 2> $O/benchlong_$W.err || { tail -20 $O/benchlong_$W.err; exit 1; }
+      timeout -k 10 400 python -u bench.py --full --workload $W --no-cpu-baseline > $O/benchlong_$W.json 2> $O/benchlong_$W.err || { tail -20 $O/benchlong_$W.err; exit 1; }
       python tools/bench_line.py $O/benchlong_$W.json ;;
     bench:*)
       W=${S#bench:}
-      timeout -k 10 300 python -u bench.py --workload $W --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_$W.json 2> $O/bench_$W.err || { tail -20 $O/bench_$W.err; exit 1; }
+      timeout -k 10 300 python -u bench.py --full --workload $W --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_$W.json 2> $O/bench_$W.err || { tail -20 $O/bench_$W.err; exit 1; }
       python tools/bench_line.py $O/bench_$W.json ;;
     rccl)
       timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-        --master-port 29517 bench.py --dist --envs 131072 --steps 200 --warmup 20 --no-cpu-baseline \
+        --master-port 29517 bench.py --full --dist --envs 131072 --steps 200 --warmup 20 --no-cpu-baseline \
         > $O/rccl.json 2> $O/rccl.err || { tail -30 $O/rccl.err; exit 1; }
       cat $O/rccl.json ;;
     ranks)
@@ -83,7 +83,7 @@ for S in "$@"; do
       rm -f $O/dg*.npz ;;  # (64 MB each: gpurun returns at most 64 MiB)
     shards)
       for N in 1048576 524288 262144 131072; do
-        timeout -k 10 300 python -u bench.py --envs $N --steps 400 --warmup 30 --no-cpu-baseline > $O/shard_$N.json 2> $O/shard_$N.err || { tail -20 $O/shard_$N.err; exit 1; }
+        timeout -k 10 300 python -u bench.py --full --envs $N --steps 400 --warmup 30 --no-cpu-baseline > $O/shard_$N.json 2> $O/shard_$N.err || { tail -20 $O/shard_$N.err; exit 1; }
         python tools/bench_line.py $O/shard_$N.json
       done ;;
     adapter)
