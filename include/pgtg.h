@@ -14,6 +14,8 @@
  *   pgtg_get_map_plan <- EpisodeMap.map_plan / save_map                 pgtg/map.py:173-184
  *   pgtg_get_squares  <- EpisodeMap.squares feature sets (feature_at)   pgtg/map.py:49-69, parser.py:13-166
  *   pgtg_get_counters <- (new) device-side env-step / episode counters
+ *   pgtg_set_episode_stats / pgtg_episode_summary <- (new, no reference function) the VecMonitor
+ *                        wrapper the reference's caller puts around the vector env  pgtg/train.py:55
  *
  * Conventions: all pointers named *_dev are device pointers (hipMalloc'd or torch data_ptr) on the
  * handle's device; everything else is host memory.  Calls on one handle are serialised by the
@@ -30,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PGTG_ABI_VERSION 7
+#define PGTG_ABI_VERSION 8
 
 /* status codes (Python facade maps them to the reference's exception types) */
 #define PGTG_OK 0
@@ -156,6 +158,14 @@ typedef struct {
   int32_t id, x, y, route, profile, patience, delay;
 } PgtgCar;
 
+/* Episodes finished in a window, over the batch (pgtg_episode_summary). */
+typedef struct {
+  uint64_t episodes, truncated_only, length_sum;
+  int32_t  length_min, length_max;      /* INT32_MAX / 0 when episodes == 0 */
+  double   return_sum;                  /* fp64 sum of the episodes' float32 returns */
+  float    return_min, return_max;      /* +INFINITY / -INFINITY when episodes == 0 */
+} PgtgEpisodeSummary;
+
 typedef struct pgtg_handle pgtg_handle;
 
 int pgtg_create(const PgtgConfig* cfg, uint64_t n_envs, int32_t device, pgtg_handle** out);
@@ -237,6 +247,25 @@ int pgtg_set_flat_outputs(pgtg_handle* h, const int32_t* order, int32_t n_order,
  * vector env returns -- into these [N] device buffers (all three or none; needs the reward, terminated
  * and truncated outputs bound).  No reference function: it replaces per-step tensor arithmetic. */
 int pgtg_set_flat_scalars(pgtg_handle* h, float* reward_f32_dev, uint8_t* dones_dev, uint8_t* truncated_only_dev);
+/* Episode return and length per env (new; no reference function: it replaces SB3's VecMonitor wrapper of
+ * pgtg/train.py:55, whose info["episode"] = {"r", "l"} feeds ep_rew_mean / ep_len_mean).  The handle
+ * keeps per env a float32 return and an int32 length; with the two [N] buffers bound, every pgtg_step
+ * (each tick of pgtg_step_many) ends with the kernel k_episode, which per env e does
+ *   ret[e] += (float)reward[e];  len[e] += 1;  ep_return[e] = ret[e];  ep_length[e] = len[e]
+ *   if (terminated[e] | truncated[e]) { the episode joins the summary;  ret[e] = 0;  len[e] = 0 }
+ * so a finished env's row holds its episode's totals, the others their running values (the reward output
+ * only, also with separate_reward_cost; the same rule with autoreset = 0, the accumulators restarting at
+ * the env's next reset).  Both buffers or neither (NULL, NULL = off; frees nothing).  The accumulators are
+ * allocated, zeroed, at the first binding and kept when other buffers are bound; pgtg_reset and
+ * pgtg_reset_unseeded zero them for the envs they reset.  They are NOT part of the state blob:
+ * pgtg_load_state zeroes them for every env and leaves the summary as it is.  Needs the reward, terminated
+ * and truncated outputs bound (PGTG_E_INVALID otherwise); while statistics are bound, pgtg_set_outputs
+ * refuses a set without one of the three (PGTG_E_INVALID, the previous outputs stay bound). */
+int pgtg_set_episode_stats(pgtg_handle* h, float* ep_return_dev, int32_t* ep_length_dev);
+/* Episodes finished since create or since the last call with reset != 0 (one row per 256 envs, updated
+ * without atomics and combined here in row order: the same bits on any device and for any step kernel).
+ * Synchronises.  PGTG_E_INVALID if statistics were never bound. */
+int pgtg_episode_summary(pgtg_handle* h, PgtgEpisodeSummary* out, int32_t reset);
 /* Re-emit the observation of every env into the bound outputs (after set_agent/add_car). */
 int pgtg_observe(pgtg_handle* h);
 /* Per-env uint64 digest of the car list into out_dev[N] (device; parity tests: the car term of

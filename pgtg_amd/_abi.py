@@ -14,7 +14,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 # PGTG_LIB selects another build of the same library (test variants, pgtg_amd/build.py VARIANTS)
 LIB_PATH = os.environ.get("PGTG_LIB") or os.path.join(PKG, "libpgtg_hip.so")
 
-PGTG_ABI_VERSION = 7
+PGTG_ABI_VERSION = 8
 MAX_TILES = 256
 MAX_CHANNELS = 128
 MAX_RULES = 8
@@ -33,6 +33,7 @@ EXPORTED = [
     "pgtg_error_count", "pgtg_window", "pgtg_num_envs", "pgtg_launch_info", "pgtg_occupancy", "pgtg_step_kernel", "pgtg_last_error", "pgtg_enable_timing",
     "pgtg_timing_read", "pgtg_measure_hbm", "pgtg_state_size", "pgtg_dump_state", "pgtg_load_state",
     "pgtg_set_to_state", "pgtg_car_digest", "pgtg_get_queue_maps", "pgtg_get_queue_overflow", "pgtg_set_flat_outputs", "pgtg_set_flat_scalars",
+    "pgtg_set_episode_stats", "pgtg_episode_summary",
 ]
 
 
@@ -87,6 +88,12 @@ class PgtgCar(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("id", "x", "y", "route", "profile", "patience", "delay")]
 
 
+class PgtgEpisodeSummary(C.Structure):
+    _fields_ = [("episodes", C.c_uint64), ("truncated_only", C.c_uint64), ("length_sum", C.c_uint64),
+                ("length_min", C.c_int32), ("length_max", C.c_int32), ("return_sum", C.c_double),
+                ("return_min", C.c_float), ("return_max", C.c_float)]
+
+
 _lib = None
 
 
@@ -133,6 +140,8 @@ def lib():
         "pgtg_get_queue_overflow": ([vp, C.POINTER(u64)], C.c_int),
         "pgtg_set_flat_outputs": ([vp, C.POINTER(C.c_int32), i32, i32, vp, vp], C.c_int),
         "pgtg_set_flat_scalars": ([vp, vp, vp, vp], C.c_int),
+        "pgtg_set_episode_stats": ([vp, vp, vp], C.c_int),
+        "pgtg_episode_summary": ([vp, C.POINTER(PgtgEpisodeSummary), i32], C.c_int),
         "pgtg_error_count": ([vp, C.POINTER(u64), C.POINTER(i32)], C.c_int),
         "pgtg_window": ([vp], C.c_int),
         "pgtg_num_envs": ([vp], u64),

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "pgtg_device.h"
+#include "pgtg_episode.h"
 
 namespace pgtg {
 namespace dv {
@@ -4589,6 +4590,10 @@ struct pgtg_handle {
   uint8_t* flat_dones = nullptr;
   uint8_t* flat_tonly = nullptr;
   int flat_dtype = 0;  // 0 float32, 1 int8
+  // episode statistics (pgtg_set_episode_stats): k_episode's arguments.  ep.ret / ep.len / ep.rows are
+  // allocated at the first binding and stay; ep.out_ret != nullptr <=> bound
+  EpisodeArgs ep{};
+  uint64_t ep_rows = 0;
 };
 
 
@@ -5306,7 +5311,29 @@ int pgtg_set_stream(pgtg_handle* h, void* stream) {
 
 int pgtg_set_outputs(pgtg_handle* h, const PgtgOutputs* o) {
   if (!h || !o) return PGTG_E_INVALID;
+  if (h->ep.out_ret && (!o->reward || !o->terminated || !o->truncated))  // (k_episode checks no pointer)
+    return fail(h, PGTG_E_INVALID, "episode statistics are bound: the reward, terminated and truncated outputs must stay");
   h->out = *o;
+  return PGTG_OK;
+}
+
+// k_episode after a step's kernels (statistics bound): the pointers were checked at bind time
+static int launch_episode(pgtg_handle* h) {
+  EpisodeArgs a = h->ep;
+  a.rew = h->out.reward;
+  a.term = h->out.terminated;
+  a.trunc = h->out.truncated;
+  hipLaunchKernelGGL(k_episode, dim3((unsigned)h->ep_rows), dim3(kEpisodeBlock), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  return PGTG_OK;
+}
+
+// the accumulators of the envs a reset restarted (once allocated)
+static int episode_zero(pgtg_handle* h, const uint8_t* mask) {
+  if (!h->ep.ret) return PGTG_OK;
+  hipLaunchKernelGGL(k_episode_zero, dim3((unsigned)h->ep_rows), dim3(kEpisodeBlock), 0, h->stream, h->ep.ret, h->ep.len,
+                     mask, h->n);
+  HIPCHK(h, hipGetLastError());
   return PGTG_OK;
 }
 
@@ -5410,6 +5437,8 @@ static int launch(pgtg_handle* h, const uint8_t* actions, const uint8_t* mask, i
     HIPCHK(h, hipEventRecord(h->evpool[h->ev_used + 1], h->stream));
     h->ev_used += 2;
   }
+  if (h->ep.out_ret && mode == MODE_STEP)
+    if (int rc = launch_episode(h)) return rc;
   return PGTG_OK;
 }
 
@@ -5447,12 +5476,14 @@ int pgtg_reset(pgtg_handle* h, const uint64_t* seeds_host, uint64_t seed_base, c
     HIPCHK(h, hipGetLastError());
   }
   if (int rc = launch(h, nullptr, mask_dev, MODE_RESET_SEEDED)) return rc;
+  if (int rc = episode_zero(h, mask_dev)) return rc;
   return queue_fill(h);
 }
 
 int pgtg_reset_unseeded(pgtg_handle* h, const uint8_t* mask_dev) {
   if (!h) return PGTG_E_INVALID;
   if (int rc = launch(h, nullptr, mask_dev, MODE_RESET_UNSEEDED)) return rc;
+  if (int rc = episode_zero(h, mask_dev)) return rc;
   return queue_fill(h);
 }
 
@@ -5859,6 +5890,10 @@ int pgtg_load_state(pgtg_handle* h, const void* buf, uint64_t bytes) {
   }
   if (h->S.tr_count) HIPCHK(h, hipMemset(h->S.tr_count, 0, 2 * sizeof(uint32_t)));
   if (h->S.qctr) HIPCHK(h, hipMemset(h->S.qctr, 0, kQctrWords * sizeof(uint32_t)));  // (dumped with full rings)
+  if (h->ep.ret) {  // the episode accumulators are not in the blob: every env starts a new count
+    HIPCHK(h, hipMemsetAsync(h->ep.ret, 0, h->n * sizeof(float), h->stream));  // (ordered with k_episode)
+    HIPCHK(h, hipMemsetAsync(h->ep.len, 0, h->n * sizeof(int32_t), h->stream));
+  }
   return PGTG_OK;
 }
 
@@ -5978,6 +6013,62 @@ int pgtg_set_flat_scalars(pgtg_handle* h, float* reward_f32_dev, uint8_t* dones_
   h->flat_rew32 = reward_f32_dev;
   h->flat_dones = dones_dev;
   h->flat_tonly = truncated_only_dev;
+  return PGTG_OK;
+}
+
+int pgtg_set_episode_stats(pgtg_handle* h, float* ep_return_dev, int32_t* ep_length_dev) {
+  if (!h) return PGTG_E_INVALID;
+  if (!ep_return_dev && !ep_length_dev) {  // off: the accumulators and the summary stay
+    h->ep.out_ret = nullptr;
+    h->ep.out_len = nullptr;
+    return PGTG_OK;
+  }
+  if (!ep_return_dev || !ep_length_dev) return fail(h, PGTG_E_INVALID, "episode statistics: both buffers or none");
+  if (!h->out.reward || !h->out.terminated || !h->out.truncated)
+    return fail(h, PGTG_E_INVALID, "episode statistics need the reward, terminated and truncated outputs");
+  if (!h->ep.rows) {  // first use: zeroed accumulators and partial rows (a zeroed row = no episode yet)
+    HIPCHK(h, hipSetDevice(h->device));
+    h->ep_rows = (h->n + kEpisodeBlock - 1) / kEpisodeBlock;
+    if (int rc = dalloc(h, &h->ep.ret, h->n)) return rc;
+    if (int rc = dalloc(h, &h->ep.len, h->n)) return rc;
+    PgtgEpisodeSummary* rows = nullptr;
+    if (int rc = dalloc(h, &rows, h->ep_rows)) return rc;
+    HIPCHK(h, hipDeviceSynchronize());  // (the memsets, before a launch on the handle's stream)
+    h->ep.rows = rows;
+    h->ep.n = h->n;
+  }
+  h->ep.out_ret = ep_return_dev;
+  h->ep.out_len = ep_length_dev;
+  return PGTG_OK;
+}
+
+int pgtg_episode_summary(pgtg_handle* h, PgtgEpisodeSummary* out, int32_t reset) {
+  if (!h || !out) return PGTG_E_INVALID;
+  if (!h->ep.rows) return fail(h, PGTG_E_INVALID, "pgtg_episode_summary: episode statistics were never bound");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  std::vector<PgtgEpisodeSummary> rows(h->ep_rows);
+  HIPCHK(h, hipMemcpy(rows.data(), h->ep.rows, rows.size() * sizeof(PgtgEpisodeSummary), hipMemcpyDeviceToHost));
+  PgtgEpisodeSummary s{};
+  s.length_min = INT32_MAX;
+  s.return_min = INFINITY;
+  s.return_max = -INFINITY;
+  for (const auto& r : rows) {  // row order: one order of the fp64 sum
+    if (!r.episodes) continue;
+    s.episodes += r.episodes;
+    s.truncated_only += r.truncated_only;
+    s.length_sum += r.length_sum;
+    s.length_min = std::min(s.length_min, r.length_min);
+    s.length_max = std::max(s.length_max, r.length_max);
+    s.return_sum = s.return_sum + r.return_sum;
+    s.return_min = std::min(s.return_min, r.return_min);
+    s.return_max = std::max(s.return_max, r.return_max);
+  }
+  *out = s;
+  if (reset) {
+    HIPCHK(h, hipMemsetAsync(h->ep.rows, 0, rows.size() * sizeof(PgtgEpisodeSummary), h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
   return PGTG_OK;
 }
 

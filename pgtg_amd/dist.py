@@ -50,6 +50,33 @@ def reduce_counters(env_steps: int, episodes: int, elapsed_s: float, device=None
     return int(cnt[0].item()), int(cnt[1].item()), float(tim[0].item())
 
 
+def reduce_episode_summary(summary: dict, device=None) -> dict:
+    """PGTGVecEnv.episode_summary() over ranks: counts and sums added (the fp64 return sum in the
+    collective's order), min / max values reduced with MIN / MAX, the means recomputed; identity without
+    a process group.  A rank without episodes contributes the empty summary's sentinels."""
+    import torch
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return dict(summary)
+    cnt = torch.tensor([summary[k] for k in ("episodes", "truncated_only", "length_sum")], dtype=torch.int64, device=device)
+    rsum = torch.tensor([summary["return_sum"]], dtype=torch.float64, device=device)
+    lmin = torch.tensor([summary["length_min"]], dtype=torch.int64, device=device)
+    lmax = torch.tensor([summary["length_max"]], dtype=torch.int64, device=device)
+    rmin = torch.tensor([summary["return_min"]], dtype=torch.float32, device=device)
+    rmax = torch.tensor([summary["return_max"]], dtype=torch.float32, device=device)
+    dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
+    dist.all_reduce(rsum, op=dist.ReduceOp.SUM)
+    for t, op in ((lmin, dist.ReduceOp.MIN), (lmax, dist.ReduceOp.MAX), (rmin, dist.ReduceOp.MIN), (rmax, dist.ReduceOp.MAX)):
+        dist.all_reduce(t, op=op)
+    n = int(cnt[0].item())
+    out = {"episodes": n, "truncated_only": int(cnt[1].item()), "length_sum": int(cnt[2].item()),
+           "length_min": int(lmin.item()), "length_max": int(lmax.item()), "return_sum": float(rsum.item()),
+           "return_min": float(rmin.item()), "return_max": float(rmax.item())}
+    out["return_mean"] = out["return_sum"] / n if n else None
+    out["length_mean"] = out["length_sum"] / n if n else None
+    return out
+
+
 def reduce_sum(values, device=None, force: bool = False) -> list[int]:
     """Element-wise sum of integer counters over ranks (identity without a process group)."""
     import torch

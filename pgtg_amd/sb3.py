@@ -20,9 +20,16 @@ carry the batch's terminal observations as one [N, D] tensor (valid on the rows 
 converted to SB3's per-env dicts only if an entry is read.  Nothing crosses PCIe in the step.  The
 flattened rows (float32 / int8) are written by the HIP kernel k_flatten inside the step (include/pgtg.h
 pgtg_set_flat_outputs) into tensors that are fresh for every step; other dtypes go through flatten_obs.
+
+`monitor=True` replaces SB3's `VecMonitor` (pgtg/train.py:55): a finished env's info gains
+`"episode": {"r": float32 return, "l": int32 length, "t": seconds since construction}`, from the
+per-env accumulators the HIP kernel k_episode keeps inside the step (include/pgtg.h
+pgtg_set_episode_stats), and `episode_summary()` gives the batch's finished episodes (count, mean / min /
+max return, mean length, truncations) without reading a single per-env dict.
 """
 from __future__ import annotations
 
+import time
 from collections.abc import Sequence
 from typing import Any
 
@@ -39,11 +46,14 @@ class VecInfos(Sequence):
     whatever the batch size; callers that read every entry pay for what they read (SB3's VecMonitor,
     which pgtg/train.py:55 wraps around the env, reads them all: `list(infos[:])` per step)."""
 
-    def __init__(self, dones, truncated, final, cost, final_rows=None):
+    def __init__(self, dones, truncated, final, cost, final_rows=None, *, ep_return=None, ep_length=None,
+                 ep_time=None):
         """final: the terminal observations, one row per env ([N, D]), or with `final_rows` one row per
-        finished env in env order (final_rows[i] = env i's row)."""
+        finished env in env order (final_rows[i] = env i's row).  ep_return / ep_length ([N] float32 /
+        int32, both or neither) and ep_time: a finished env's dict gains VecMonitor's "episode" entry."""
         self._dones, self._trunc, self._final, self._cost = dones, truncated, final, cost
         self._rows = final_rows
+        self._ep_r, self._ep_l, self._ep_t = ep_return, ep_length, ep_time
         # env i's dict, built on its first read and returned on every later one: SB3 wrappers
         # (VecNormalize, VecFrameStack, VecTransposeImage) rewrite infos[i]["terminal_observation"] in
         # place and rely on reading their own value back, as from SubprocVecEnv's list
@@ -58,6 +68,8 @@ class VecInfos(Sequence):
         if self._dones[i]:
             d["terminal_observation"] = self._final[i if self._rows is None else int(self._rows[i])]
             d["TimeLimit.truncated"] = bool(self._trunc[i])
+            if self._ep_r is not None:
+                d["episode"] = {"r": np.float32(self._ep_r[i]), "l": np.int32(self._ep_l[i]), "t": self._ep_t}
         if self._cost is not None:
             d["cost"] = float(self._cost[i])
         return d
@@ -98,18 +110,25 @@ class VecInfos(Sequence):
 
 class DeviceVecInfos(Sequence):
     """The infos of a `device_obs` step: the batch's tensors on the device (`dones`, `truncated`,
-    `terminal_observation` [N, D] with valid rows where done, `cost`), and SB3's per-env dicts on
-    demand (the first per-env read copies the masks to the host once)."""
+    `terminal_observation` [N, D] with valid rows where done, `cost`; with monitor=True `episode_return`
+    and `episode_length`, a finished env's entries being its episode's totals), and SB3's per-env dicts
+    on demand (the first per-env read copies the masks to the host once)."""
 
-    def __init__(self, dones, truncated, final, cost):
+    def __init__(self, dones, truncated, final, cost, *, episode_return=None, episode_length=None,
+                 episode_time=None):
         self.dones, self.truncated, self.terminal_observation, self.cost = dones, truncated, final, cost
+        self.episode_return, self.episode_length, self.episode_time = episode_return, episode_length, episode_time
         self._host: VecInfos | None = None
 
     def _h(self) -> VecInfos:
         if self._host is None:
             d = self.dones.cpu().numpy()
+            ep = {}
+            if self.episode_return is not None:
+                ep = dict(ep_return=self.episode_return.cpu().numpy(), ep_length=self.episode_length.cpu().numpy(),
+                          ep_time=self.episode_time)
             self._host = VecInfos(d, self.truncated.cpu().numpy(), self.terminal_observation,
-                                  None if self.cost is None else self.cost.cpu().numpy())
+                                  None if self.cost is None else self.cost.cpu().numpy(), **ep)
         return self._host
 
     def __len__(self) -> int:
@@ -125,9 +144,13 @@ class DeviceVecInfos(Sequence):
 class PGTGSB3VecEnv:
     def __init__(self, num_envs: int, map_path: str | None = None, *, max_episode_steps: int | None = 100,
                  device: int | None = None, seed: int = 0, device_obs: bool = False, obs_dtype=None,
-                 zero_copy: bool = False, **kwargs: Any):
+                 zero_copy: bool = False, monitor: bool = False, **kwargs: Any):
         self.venv = PGTGVecEnv(num_envs, map_path, device=device, autoreset=True,
                                max_episode_steps=max_episode_steps, **kwargs)
+        self.monitor = bool(monitor)
+        self._t_start = time.time()
+        if self.monitor:  # (checked once here; the device path rebinds fresh tensors every step)
+            self._ep_d = self.venv.enable_episode_stats()
         self.spec = self.venv.spec
         self.num_envs = num_envs
         self.obs_dim = flat_dim(self.spec)
@@ -208,9 +231,24 @@ class PGTGSB3VecEnv:
             raise KeyError(int(a[(a < 0) | (a > 8)][0]))
         self._actions = torch.as_tensor(a.astype(np.uint8))
 
+    def episode_summary(self, reset: bool = True) -> dict:
+        """The batch's finished episodes (PGTGVecEnv.episode_summary); needs monitor=True."""
+        return self.venv.episode_summary(reset)
+
+    def _episode_kw(self, prefix: str) -> dict:
+        """The infos' episode arguments of this step (monitor=True); the device path's tensors are the
+        caller's, so the next step binds fresh ones."""
+        ep_r, ep_l = self._ep_d
+        return {prefix + "_return": ep_r, prefix + "_length": ep_l,
+                prefix + "_time": round(time.time() - self._t_start, 6)}
+
     def step_wait(self):
         import torch
         kflat = self._kernel_flat()
+        if self.monitor and self.device_obs:
+            n, dev = self.num_envs, self.venv.device
+            self._ep_d = (torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+            self.venv._bind_episode_ptrs(*self._ep_d)
         if kflat:  # the rows are written by k_flatten in the step: no torch work on the observations
             flat_d, final_d = self._bind_flat(final=True)
             if self.device_obs:  # ... nor on the rewards and done flags (written by the same pass)
@@ -225,12 +263,13 @@ class PGTGSB3VecEnv:
                 infos["cost"] = v.cost
         else:
             obs, reward, term, trunc, infos = self.venv.step(self._actions)
+        ep = self._episode_kw("episode") if self.monitor and self.device_obs else {}
         if self.device_obs and kflat:
             cost = infos.get("cost")
             if cost is not None:  # (the venv's output buffer, rewritten by the next step)
                 cost = cost.clone()
             rew32, dones, tonly = sc
-            return flat_d, rew32, dones, DeviceVecInfos(dones, tonly, final_d, cost)
+            return flat_d, rew32, dones, DeviceVecInfos(dones, tonly, final_d, cost, **ep)
         if self.device_obs:
             dones = term | trunc
             if kflat:
@@ -242,7 +281,7 @@ class PGTGSB3VecEnv:
             cost = infos.get("cost")
             if cost is not None:  # (the venv's output buffer, rewritten by the next step)
                 cost = cost.clone()
-            return (flat, reward.to(torch.float32), dones, DeviceVecInfos(dones, trunc & ~term, final, cost))
+            return (flat, reward.to(torch.float32), dones, DeviceVecInfos(dones, trunc & ~term, final, cost, **ep))
         # host arrays (SB3's VecEnv contract): one copy per step into page-locked buffers, and the
         # terminal observations of the finished envs only.  The buffers are fresh for every step (torch's
         # caching host allocator: a block returns to the cache only when the arrays over it are dropped),
@@ -256,6 +295,9 @@ class PGTGSB3VecEnv:
         cost = None
         if "cost" in infos:
             h["cost"].copy_(infos["cost"], non_blocking=True)
+        if self.monitor:
+            h["ep_r"].copy_(self._ep_d[0], non_blocking=True)
+            h["ep_l"].copy_(self._ep_d[1], non_blocking=True)
         torch.cuda.current_stream(self.venv.device).synchronize()
         term_h, trunc_h = h["term"].numpy().astype(bool), h["trunc"].numpy().astype(bool)
         dones = term_h | trunc_h
@@ -267,18 +309,25 @@ class PGTGSB3VecEnv:
             rows[idx] = np.arange(idx.size)
         if "cost" in infos:
             cost = h["cost"].numpy().copy()
-        return h["obs"].numpy(), h["rew"].numpy(), dones, VecInfos(dones, trunc_h & ~term_h, final, cost, rows)
+        if self.monitor:
+            ep = dict(ep_return=h["ep_r"].numpy(), ep_length=h["ep_l"].numpy(),
+                      ep_time=round(time.time() - self._t_start, 6))
+        return h["obs"].numpy(), h["rew"].numpy(), dones, VecInfos(dones, trunc_h & ~term_h, final, cost, rows, **ep)
 
     def _new_host_buffers(self) -> dict:
         import torch
 
         def pinned(shape, dtype):
             return torch.empty(shape, dtype=dtype, pin_memory=True)
-        return {"obs": pinned((self.num_envs, self.obs_dim), torch.float32),
-                "rew": pinned((self.num_envs,), torch.float32),
-                "term": pinned((self.num_envs,), torch.uint8),
-                "trunc": pinned((self.num_envs,), torch.uint8),
-                "cost": pinned((self.num_envs,), torch.float64)}
+        h = {"obs": pinned((self.num_envs, self.obs_dim), torch.float32),
+             "rew": pinned((self.num_envs,), torch.float32),
+             "term": pinned((self.num_envs,), torch.uint8),
+             "trunc": pinned((self.num_envs,), torch.uint8),
+             "cost": pinned((self.num_envs,), torch.float64)}
+        if self.monitor:
+            h["ep_r"] = pinned((self.num_envs,), torch.float32)
+            h["ep_l"] = pinned((self.num_envs,), torch.int32)
+        return h
 
     def _host_buffers(self) -> dict:
         if not self.zero_copy:

@@ -87,6 +87,7 @@ class PGTGVecEnv:
         _check(self._lib.pgtg_set_outputs(h, C.byref(o)), h)
         self.has_cars = self.spec.traffic_density > 0 or min_car_capacity > 0  # the handle keeps car lists
         self._seeded = False
+        self._episode_refs = ()  # (ep_return, ep_length) while episode statistics are bound
 
     # -- plumbing ------------------------------------------------------------------------------
     def _bind_stream(self):
@@ -161,6 +162,9 @@ class PGTGVecEnv:
             infos["_final_observation"] = done
         if self.cost is not None:
             infos["cost"] = self.cost
+        if self._episode_refs:
+            infos["episode_return"], infos["episode_length"] = self._episode_refs
+            infos["_episode"] = self.terminated | self.truncated
         return self.observation(), self.reward, self.terminated, self.truncated, infos
 
     def step_launch(self, actions) -> None:
@@ -286,6 +290,47 @@ class PGTGVecEnv:
         _check(self._lib.pgtg_set_flat_outputs(self._h, self._flat_order, len(self._flat_order), dtype_code,
                                                ptr(flat), ptr(final_flat)), self._h)
         self._flat_refs = (flat, final_flat)  # (the handle writes into them: keep them alive)
+
+    # -- episode statistics (SB3's VecMonitor for the batch, pgtg/train.py:55) -----------------------
+    def enable_episode_stats(self, ep_return=None, ep_length=None):
+        """Have every step also write each env's episode return (float32) and length (int32) so far
+        into [N] device tensors -- a finished env's entry is its episode's totals, as in VecMonitor's
+        info["episode"] -- and count the finished episodes into the batch summary (include/pgtg.h
+        pgtg_set_episode_stats; the HIP kernel k_episode, no torch work).  Tensors not given are
+        allocated; returns (ep_return, ep_length)."""
+        import torch
+        if ep_return is None:
+            ep_return = torch.zeros(self.num_envs, dtype=torch.float32, device=self.device)
+        if ep_length is None:
+            ep_length = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        for t, dt in zip((ep_return, ep_length), (torch.float32, torch.int32)):
+            if t.dtype != dt or tuple(t.shape) != (self.num_envs,) or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"episode statistics: contiguous [{self.num_envs}] {dt} tensors on {self.device}")
+        self._bind_episode_ptrs(ep_return, ep_length)
+        return ep_return, ep_length
+
+    def _bind_episode_ptrs(self, ep_return, ep_length) -> None:
+        """Rebind tensors of the shape and dtype enable_episode_stats checked (the per-step path of
+        PGTGSB3VecEnv); the handle's accumulators and summary are kept."""
+        _check(self._lib.pgtg_set_episode_stats(self._h, C.c_void_p(ep_return.data_ptr()),
+                                                C.c_void_p(ep_length.data_ptr())), self._h)
+        self._episode_refs = (ep_return, ep_length)  # (the handle writes into them: keep them alive)
+
+    def disable_episode_stats(self) -> None:
+        _check(self._lib.pgtg_set_episode_stats(self._h, None, None), self._h)
+        self._episode_refs = ()
+
+    def episode_summary(self, reset: bool = True) -> dict:
+        """The episodes finished since the statistics were enabled or since the last read with reset=True:
+        the fields of PgtgEpisodeSummary plus return_mean and length_mean (None without episodes).
+        Host-synchronising."""
+        s = _abi.PgtgEpisodeSummary()
+        _check(self._lib.pgtg_episode_summary(self._h, C.byref(s), int(bool(reset))), self._h)
+        d = {f: getattr(s, f) for f, _ in s._fields_}
+        n = d["episodes"]
+        d["return_mean"] = d["return_sum"] / n if n else None
+        d["length_mean"] = d["length_sum"] / n if n else None
+        return d
 
     def observe(self):
         """Re-emit every env's observation (after set_agent / add_car)."""
