@@ -111,6 +111,9 @@ def lib():
         L.orc_bench.argtypes = [C.POINTER(OrcConfig), C.c_int, C.c_int, C.c_uint64, C.c_uint64]
         L.orc_rollout_digest.restype = C.c_int
         L.orc_rollout_digest.argtypes = [C.POINTER(OrcConfig), C.c_int64, C.c_uint64, C.c_int, C.c_uint64, C.c_void_p]
+        L.orc_rollout_digest_tl.restype = C.c_int
+        L.orc_rollout_digest_tl.argtypes = [C.POINTER(OrcConfig), C.c_int64, C.c_uint64, C.c_int, C.c_uint64, C.c_int,
+                                            C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -193,11 +196,15 @@ def _parallel(fn, n_envs: int, threads: int, chunk_min: int = 256):
         return list(ex.map(lambda b: fn(*b), bounds))
 
 
-def rollout_digest(spec, n_envs: int, steps: int, act_seed: int, env_offset: int = 0, threads: int = 0) -> np.ndarray:
+def rollout_digest(spec, n_envs: int, steps: int, act_seed: int, env_offset: int = 0, threads: int = 0,
+                   max_episode_steps: int = 0, flags_out: bool = False):
     """[steps, n_envs] uint64 output digests of global envs env_offset..+n_envs (seed = global index,
-    actions = the GPU's splitmix hash), the formula of pgtg_amd/digest.py."""
+    actions = the GPU's splitmix hash), the formula of pgtg_amd/digest.py.  max_episode_steps > 0 runs
+    the rollout behind gymnasium's TimeLimit; flags_out=True returns (digests, flags), flags a
+    [steps, n_envs] uint8 array with bit 0 terminated and bit 1 truncated."""
     c = config_from_spec(spec)
     out = np.zeros((steps, n_envs), dtype=np.uint64)
+    flags = np.zeros((steps, n_envs), dtype=np.uint8)
     # warm the library's one-time tables on this thread before fanning out
     e = lib().orc_create(C.byref(c))
     lib().orc_destroy(e)
@@ -206,14 +213,17 @@ def rollout_digest(spec, n_envs: int, steps: int, act_seed: int, env_offset: int
         if hi <= lo:
             return 0
         part = np.zeros((steps, hi - lo), dtype=np.uint64)
-        rc = lib().orc_rollout_digest(C.byref(c), hi - lo, env_offset + lo, steps, act_seed, part.ctypes.data)
+        fpart = np.zeros((steps, hi - lo), dtype=np.uint8)
+        rc = lib().orc_rollout_digest_tl(C.byref(c), hi - lo, env_offset + lo, steps, act_seed, int(max_episode_steps),
+                                         part.ctypes.data, fpart.ctypes.data)
         if rc:
             raise RuntimeError("oracle rollout failed")
         out[:, lo:hi] = part
+        flags[:, lo:hi] = fpart
         return hi - lo
 
     _parallel(run, n_envs, threads or host_threads())
-    return out
+    return (out, flags) if flags_out else out
 
 
 def bench_parallel(spec, n_envs: int, steps: int, threads: int, act_seed: int = 12345) -> int:

@@ -1428,7 +1428,12 @@ int64_t orc_bench(const orc_config* cfg, int n_envs, int steps, uint64_t seed_ba
  * GPU's k_random_actions).  digest[t * n_envs + i] = pgtg_amd/digest.py's formula over that step's
  * outputs: sum of W(j) over the observation's set bytes j, W(D + k) times the small outputs, and the
  * terminal observation's bytes at W(D + 16 + j) when the env finished, and with traffic the car list
- * after the step (dg_cars; all arithmetic mod 2^64). */
+ * after the step (dg_cars; all arithmetic mod 2^64).
+ * orc_rollout_digest_tl runs the rollout behind gymnasium's TimeLimit(max_episode_steps) (0: no
+ * limit): an env counts its steps since its last reset, a step is truncated once that count reaches
+ * the limit (also when the same step terminated), and a terminated or truncated env is reset
+ * unseeded in the same step.  flags (may be NULL) receives bit 0 terminated, bit 1 truncated per
+ * (step, env). */
 static uint64_t dg_w(uint64_t j) {
   uint64_t z = j + 1 + 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -1466,8 +1471,8 @@ static uint64_t dg_cars(const orc_env* e) {
   }
   return d;
 }
-int orc_rollout_digest(const orc_config* cfg, int64_t n_envs, uint64_t env_offset, int steps, uint64_t act_seed,
-                       uint64_t* digest) {
+int orc_rollout_digest_tl(const orc_config* cfg, int64_t n_envs, uint64_t env_offset, int steps, uint64_t act_seed,
+                          int max_episode_steps, uint64_t* digest, uint8_t* flags) {
   int win = cfg->sliding ? 1 + 2 * cfg->sliding_size : TILE;
   int D = cfg->n_channels * win * win;
   uint8_t* obs = (uint8_t*)malloc((size_t)D + 1);
@@ -1480,6 +1485,7 @@ int orc_rollout_digest(const orc_config* cfg, int64_t n_envs, uint64_t env_offse
       free(obs);
       return -1;
     }
+    int elapsed = 0; /* steps since the last reset */
     for (int t = 0; t < steps; t++) {
       uint64_t z = act_seed ^ ((uint64_t)t * 0x9E3779B97F4A7C15ull) ^ (g * 0xD1B54A32D192ED03ull);
       z += 0x9E3779B97F4A7C15ull;
@@ -1492,9 +1498,13 @@ int orc_rollout_digest(const orc_config* cfg, int64_t n_envs, uint64_t env_offse
         free(obs);
         return -1;
       }
+      elapsed++;
+      out.truncated = max_episode_steps > 0 && elapsed >= max_episode_steps;
       uint64_t d = 0;
       orc_out step_out = out;
-      if (out.terminated) {
+      if (flags) flags[(size_t)t * (size_t)n_envs + (size_t)i] = (uint8_t)((out.terminated != 0) | (out.truncated != 0) << 1);
+      if (out.terminated || out.truncated) {
+        elapsed = 0;
         d += dg_obs(obs, D, (uint64_t)D + 16);
         if (orc_reset(e, -1, obs, &out)) {
           orc_destroy(e);
@@ -1516,4 +1526,8 @@ int orc_rollout_digest(const orc_config* cfg, int64_t n_envs, uint64_t env_offse
   }
   free(obs);
   return 0;
+}
+int orc_rollout_digest(const orc_config* cfg, int64_t n_envs, uint64_t env_offset, int steps, uint64_t act_seed,
+                       uint64_t* digest) {
+  return orc_rollout_digest_tl(cfg, n_envs, env_offset, steps, act_seed, 0, digest, NULL);
 }

@@ -4534,9 +4534,11 @@ __global__ void __launch_bounds__(256, 6) k_flatten(FlatArgs a) {
   }
 }
 
-__global__ void k_fill_seeds(uint64_t* seed, uint64_t n, uint64_t base, uint64_t offset) {
+// The seeds of a seeded reset, for the envs it resets only (mask null: all): an env outside the mask
+// keeps its seed, which its later unseeded resets spawn their streams from.  src null: base + i.
+__global__ void k_fill_seeds(uint64_t* seed, uint64_t n, uint64_t base, const uint64_t* src, const uint8_t* mask) {
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) seed[i] = base + offset + i;
+  if (i < n && (mask == nullptr || mask[i] != 0)) seed[i] = src ? src[i] : base + i;
 }
 
 }  // namespace pgtg
@@ -4560,6 +4562,7 @@ struct pgtg_handle {
   std::vector<void*> allocs;
   std::string err;
   uint64_t seed_offset = 0;  // global index of env 0 (for sharded runs)
+  uint64_t* seed_stage = nullptr;  // a masked reset's seed list on the device (allocated at the first one)
   int tune_epb = 0, tune_obs_sub = 0, tune_kt_grid = 0, tune_kt_cap = 0, tune_kt_wpc = 0;  // PgtgConfig.tune_*
   int timing = 0;             // bracket every `timing`-th step launch with an event pair (0: off)
   uint64_t step_launches = 0;
@@ -5468,11 +5471,18 @@ static int queue_fill(pgtg_handle* h) {
 int pgtg_reset(pgtg_handle* h, const uint64_t* seeds_host, uint64_t seed_base, const uint8_t* mask_dev) {
   if (!h) return PGTG_E_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
-  if (seeds_host) {
+  if (seeds_host && !mask_dev) {
     HIPCHK(h, hipMemcpyAsync(h->S.seed, seeds_host, h->n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
   } else {
+    const uint64_t* src = nullptr;
+    if (seeds_host) {  // a masked reset with a seed list: staged, then copied for the masked envs
+      if (!h->seed_stage)
+        if (int rc = dalloc(h, &h->seed_stage, h->n)) return rc;
+      HIPCHK(h, hipMemcpyAsync(h->seed_stage, seeds_host, h->n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+      src = h->seed_stage;
+    }
     hipLaunchKernelGGL(k_fill_seeds, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->S.seed, h->n,
-                       seed_base, (uint64_t)0);
+                       seed_base, src, mask_dev);
     HIPCHK(h, hipGetLastError());
   }
   if (int rc = launch(h, nullptr, mask_dev, MODE_RESET_SEEDED)) return rc;

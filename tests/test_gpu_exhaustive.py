@@ -17,54 +17,16 @@ formulas to each other), so whole batches are compared without copying them to t
               crowded squares, spawner lists beyond the staged first 24)
   feature variants at batch sizes of every launch shape, incl. forced workgroup/sub-batch shapes.
 """
-import warnings
-
 import numpy as np
 import pytest
 import torch
 
 import helpers  # noqa: F401
-from oracle import oracle
+from digest_parity import _compare, _spec
 from oracle.oracle import OracleEnv
 from pgtg_amd import config as cfg
 
 pytestmark = pytest.mark.gpu
-
-ACT_SEED = 0xA11CE
-
-
-def _spec(kw):
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        return cfg.make_spec(**kw)
-
-
-def _gpu_digests(spec, n, T, tune=None):
-    from pgtg_amd.digest import Digest
-    from pgtg_amd.vector import PGTGVecEnv
-    env = PGTGVecEnv(n, spec=spec, device=0, tune=tune)
-    try:
-        env.reset(seed=0)
-        dg = Digest(env)
-        out = np.zeros((T, n), dtype=np.uint64)
-        for t in range(T):
-            env.step_random(ACT_SEED, t)
-            out[t] = dg.step_digest().cpu().numpy().view(np.uint64)
-        return out, env.step_kernel(), env.launch_info(), env.queue_overflow()
-    finally:
-        env.close()
-
-
-def _compare(spec, n, T, tune=None, tag="", min_distinct=1000):
-    got, kern, shape, ovf = _gpu_digests(spec, n, T, tune)
-    ref = oracle.rollout_digest(spec, n, T, ACT_SEED)
-    # the comparison has teeth: the rollout visits many distinct outputs.  Observations are local
-    # 9x9 windows, so envs on small maps share digests (3x3 maps: 4 096 envs x 100 steps give 7 326
-    # distinct ones, 262 144 x 20 give 13 072)
-    assert len(np.unique(ref)) >= min(ref.size // 4, min_distinct), "degenerate digests"
-    bad = np.argwhere(got != ref)
-    assert bad.size == 0, (f"{tag} {kern} {shape}: {len(bad)} (step, env) digests differ, first {bad[:8].tolist()}")
-    return ovf
 
 
 # every feature name of the reference's vocabulary (pgtg/environment.py:1387-1445) plus names it does
