@@ -16,6 +16,8 @@
  *   pgtg_get_counters <- (new) device-side env-step / episode counters
  *   pgtg_set_episode_stats / pgtg_episode_summary <- (new, no reference function) the VecMonitor
  *                        wrapper the reference's caller puts around the vector env  pgtg/train.py:55
+ *   pgtg_snapshot_*   <- copy.deepcopy(env) / env.clone() for single envs of the batch, on the device
+ *                        environment.py:1283-1299, pgtg/evaluator.py:98-110
  *
  * Conventions: all pointers named *_dev are device pointers (hipMalloc'd or torch data_ptr) on the
  * handle's device; everything else is host memory.  Calls on one handle are serialised by the
@@ -32,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PGTG_ABI_VERSION 8
+#define PGTG_ABI_VERSION 9
 
 /* status codes (Python facade maps them to the reference's exception types) */
 #define PGTG_OK 0
@@ -221,6 +223,40 @@ int pgtg_add_car(pgtg_handle* h, uint64_t env, int32_t x, int32_t y, int32_t rou
 int pgtg_state_size(pgtg_handle* h, uint64_t* bytes);
 int pgtg_dump_state(pgtg_handle* h, void* buf, uint64_t bytes);
 int pgtg_load_state(pgtg_handle* h, const void* buf, uint64_t bytes);
+/* Device-resident snapshots: single envs saved, restored and forked without leaving the GPU (the
+ * deepcopy of PGTGEnv.light_step, environment.py:1283-1299, and the env.clone() of Evaluator.evaluate,
+ * pgtg/evaluator.py:98-110, for any subset of a batch).  A snapshot owns device arrays with the layouts
+ * of the handle's per-env state sections (everything in the state blob but the batch-wide counters),
+ * allocated zeroed for `slots` envs; `slots` need not be the handle's batch size.  It records the
+ * handle's configuration hash, the shape fields of the blob header (tile count, car capacity and slots,
+ * plan stride, spawner capacity, visited words, ring entry words), the map ring's depth and the device:
+ * pgtg_snapshot_save / _load accept ANY handle on that device for which all of these are equal -- a
+ * snapshot saved from one handle loads into another handle of another batch size -- and refuse every
+ * other handle with PGTG_E_INVALID and a message on that handle, launching nothing.  (The ring depth
+ * follows the map-queue step kernel, k_envq 2 / k_envb 3, which tune_queue_mode 0 picks from the batch
+ * size: fix it with tune_queue_mode to share snapshots between batches of very different sizes.)
+ *   save: env env_idx_dev[k] of h -> slot slot_idx_dev[k];   load: slot slot_idx_dev[k] -> env
+ *   env_idx_dev[k] of h, for k < count.  Index arrays are uint32 device arrays; NULL = the identity k.
+ * One launch of k_state_copy (after the pending map-ring refills, as before pgtg_dump_state) on the
+ * handle's stream: neither call synchronises, and the snapshot's contents are ordered with that stream --
+ * a save on one handle's stream and a load on another's need the caller's event between them, or one
+ * stream for both handles.  A pair with an index outside its side is skipped.  A slot may be loaded into
+ * many envs in one call (fork); two pairs with the same DESTINATION in one call are the caller's error:
+ * that env or slot ends up with an unspecified mix of the two sources (nothing outside it is touched).
+ * Loading a slot that was never saved gives an env of zero bytes, not a valid episode.  Outputs are not
+ * state: call pgtg_observe after a load.  The TimeLimit step count is in the agent record and travels
+ * with the env; the episode accumulators of pgtg_set_episode_stats are not state: a load zeroes them for
+ * the envs it wrote and leaves the summary as it is.  count = 0 is a no-op.  pgtg_snapshot_destroy waits
+ * for the device.  pgtg_snapshot_bytes: the device memory the snapshot holds and the state bytes of one
+ * env (what a save or a load reads and writes per pair). */
+typedef struct pgtg_snapshot pgtg_snapshot;
+int pgtg_snapshot_create(pgtg_handle* h, uint64_t slots, pgtg_snapshot** out);
+int pgtg_snapshot_destroy(pgtg_snapshot* s);
+int pgtg_snapshot_bytes(const pgtg_snapshot* s, uint64_t* device_bytes, uint64_t* bytes_per_env);
+int pgtg_snapshot_save(pgtg_handle* h, pgtg_snapshot* s, const uint32_t* env_idx_dev, const uint32_t* slot_idx_dev,
+                       uint64_t count);
+int pgtg_snapshot_load(pgtg_handle* h, const pgtg_snapshot* s, const uint32_t* slot_idx_dev, const uint32_t* env_idx_dev,
+                       uint64_t count);
 /* PGTGEnv.set_to_state(state) (environment.py:1301-1342) for one env: position, velocity, flat tire
  * and the car list (patience/delay 0; next car id = last id + 1 if any cars).  Synchronises. */
 int pgtg_set_to_state(pgtg_handle* h, uint64_t env, int32_t x, int32_t y, int32_t vx, int32_t vy, int32_t flat_tire,

@@ -3,6 +3,7 @@
 Drop-in for the reference's hot path (Inuri04/pgtg `PGTGEnv.step/reset`, registered as "pgtg-v4"):
   PGTGVecEnv  -- N independent episodes in lockstep on one GPU (HIP kernels via include/pgtg.h)
   PGTGEnv     -- single-env Gymnasium-style facade with the reference's constructor and returns
+  Snapshot    -- single envs of a batch saved, restored and forked on the device (PGTGVecEnv.snapshot)
 """
 from .config import EnvSpec, make_spec  # noqa: F401
 
@@ -10,9 +11,9 @@ __version__ = "0.5.0"  # the reference's pgtg/__init__.py version this build mir
 
 
 def __getattr__(name):
-    if name == "PGTGVecEnv":
-        from .vector import PGTGVecEnv
-        return PGTGVecEnv
+    if name in ("PGTGVecEnv", "Snapshot", "fork_indices"):  # (device-resident snapshots of single envs)
+        from . import vector
+        return getattr(vector, name)
     if name == "PGTGEnv":
         from .env import PGTGEnv
         return PGTGEnv

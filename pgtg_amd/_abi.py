@@ -14,7 +14,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 # PGTG_LIB selects another build of the same library (test variants, pgtg_amd/build.py VARIANTS)
 LIB_PATH = os.environ.get("PGTG_LIB") or os.path.join(PKG, "libpgtg_hip.so")
 
-PGTG_ABI_VERSION = 8
+PGTG_ABI_VERSION = 9
 MAX_TILES = 256
 MAX_CHANNELS = 128
 MAX_RULES = 8
@@ -34,6 +34,7 @@ EXPORTED = [
     "pgtg_timing_read", "pgtg_measure_hbm", "pgtg_state_size", "pgtg_dump_state", "pgtg_load_state",
     "pgtg_set_to_state", "pgtg_car_digest", "pgtg_get_queue_maps", "pgtg_get_queue_overflow", "pgtg_set_flat_outputs", "pgtg_set_flat_scalars",
     "pgtg_set_episode_stats", "pgtg_episode_summary",
+    "pgtg_snapshot_create", "pgtg_snapshot_destroy", "pgtg_snapshot_bytes", "pgtg_snapshot_save", "pgtg_snapshot_load",
 ]
 
 
@@ -142,6 +143,11 @@ def lib():
         "pgtg_set_flat_scalars": ([vp, vp, vp, vp], C.c_int),
         "pgtg_set_episode_stats": ([vp, vp, vp], C.c_int),
         "pgtg_episode_summary": ([vp, C.POINTER(PgtgEpisodeSummary), i32], C.c_int),
+        "pgtg_snapshot_create": ([vp, u64, C.POINTER(vp)], C.c_int),
+        "pgtg_snapshot_destroy": ([vp], C.c_int),
+        "pgtg_snapshot_bytes": ([vp, C.POINTER(u64), C.POINTER(u64)], C.c_int),
+        "pgtg_snapshot_save": ([vp, vp, vp, vp, u64], C.c_int),
+        "pgtg_snapshot_load": ([vp, vp, vp, vp, u64], C.c_int),
         "pgtg_error_count": ([vp, C.POINTER(u64), C.POINTER(i32)], C.c_int),
         "pgtg_window": ([vp], C.c_int),
         "pgtg_num_envs": ([vp], u64),

@@ -27,6 +27,7 @@
 
 #include "pgtg_device.h"
 #include "pgtg_episode.h"
+#include "pgtg_snapshot.h"
 
 namespace pgtg {
 namespace dv {
@@ -5757,10 +5758,14 @@ int pgtg_add_car(pgtg_handle* h, uint64_t env, int32_t x, int32_t y, int32_t rou
 // scratch (its counters are zeroed on load).  Blob: PgtgStateHeader, n_sections x {id, pad, bytes},
 // then each section's bytes at a 16-byte aligned offset.
 namespace {
+// One list for the blob and for the per-env copies (pgtg_snapshot.h): a section's bytes follow from its
+// layout, so that the two cannot drift apart.
 struct StateSection {
   uint32_t id;
   void* ptr;
-  uint64_t bytes;
+  uint32_t kind;   // kSecRows / kSecSlots / kSecBatch
+  uint64_t row;    // kSecRows: bytes per env; kSecSlots: rows of 4-byte elements; kSecBatch: bytes
+  uint64_t bytes;  // of the whole section
 };
 struct PgtgStateHeader {
   char magic[4];  // "PGTS"
@@ -5788,32 +5793,35 @@ static std::vector<StateSection> state_sections(pgtg_handle* h) {
   const DevState& S = h->S;
   const uint64_t n = h->n;
   std::vector<StateSection> v;
-  auto add = [&](uint32_t id, void* p, uint64_t b) {
-    if (p) v.push_back({id, p, b});
+  auto rows = [&](uint32_t id, void* p, uint64_t row_bytes) {  // [n][row_bytes]
+    if (p) v.push_back({id, p, kSecRows, row_bytes, n * row_bytes});
   };
-  add(1, S.rec, n * sizeof(EnvRec));
-  add(2, S.seed, n * 8);
-  add(3, S.plan, n * (uint64_t)c.plan_stride * 2);
-  add(4, S.err, n);
-  add(5, S.counters, 16);
+  auto slots = [&](uint32_t id, void* p, uint64_t nrows) {  // [nrows][n] words
+    if (p) v.push_back({id, p, kSecSlots, nrows, nrows * n * 4});
+  };
+  rows(1, S.rec, sizeof(EnvRec));
+  rows(2, S.seed, 8);
+  rows(3, S.plan, (uint64_t)c.plan_stride * 2);
+  rows(4, S.err, 1);
+  if (S.counters) v.push_back({5, S.counters, kSecBatch, 16, 16});
   const DevStream* st[4] = {&S.car, &S.ice, &S.broken, &S.sand};
   for (uint32_t k = 0; k < 4; k++) {
-    add(10 + 5 * k, st[k]->shi, n * 8);
-    add(11 + 5 * k, st[k]->slo, n * 8);
-    add(12 + 5 * k, st[k]->ihi, n * 8);
-    add(13 + 5 * k, st[k]->ilo, n * 8);
-    add(14 + 5 * k, st[k]->buf, n * 8);
+    rows(10 + 5 * k, st[k]->shi, 8);
+    rows(11 + 5 * k, st[k]->slo, 8);
+    rows(12 + 5 * k, st[k]->ihi, 8);
+    rows(13 + 5 * k, st[k]->ilo, 8);
+    rows(14 + 5 * k, st[k]->buf, 8);
   }
-  add(30, S.visited, n * (uint64_t)c.vis_words * 4);
-  add(31, S.car_w0, (uint64_t)c.car_slots * n * 4);
-  add(32, S.car_w1, (uint64_t)c.car_slots * n * 4);
-  add(33, S.car_id, (uint64_t)c.car_slots * n * 4);
-  add(34, S.traf, n * sizeof(uint4));
-  add(36, S.occ, (uint64_t)c.nt * 4 * n * 4);
-  add(35, S.spawners, (uint64_t)S.sp_pitch * n * 2);
-  add(37, S.fresh, (uint64_t)S.fresh_dw * n * 4);
-  add(40, S.qbuf, n * (uint64_t)queue_depth(h) * (uint64_t)c.qrec_dw * 4);
-  add(41, S.qstate, n);
+  rows(30, S.visited, (uint64_t)c.vis_words * 4);
+  slots(31, S.car_w0, (uint64_t)c.car_slots);
+  slots(32, S.car_w1, (uint64_t)c.car_slots);
+  slots(33, S.car_id, (uint64_t)c.car_slots);
+  rows(34, S.traf, sizeof(uint4));
+  slots(36, S.occ, (uint64_t)c.nt * 4);
+  rows(35, S.spawners, (uint64_t)S.sp_pitch * 2);
+  rows(37, S.fresh, (uint64_t)S.fresh_dw * 4);
+  rows(40, S.qbuf, (uint64_t)queue_depth(h) * (uint64_t)c.qrec_dw * 4);
+  rows(41, S.qstate, 1);
   return v;
 }
 
@@ -5905,6 +5913,159 @@ int pgtg_load_state(pgtg_handle* h, const void* buf, uint64_t bytes) {
     HIPCHK(h, hipMemsetAsync(h->ep.len, 0, h->n * sizeof(int32_t), h->stream));
   }
   return PGTG_OK;
+}
+
+// ---- device-resident snapshots: per-env save, load and fork (pgtg_snapshot.h) -------------------
+// A snapshot owns one array per per-env state section of the handle it was created from, with that
+// section's layout, for `slots` envs.  What it records decides which handles may use it: the shape
+// fields of the blob header, the configuration hash, the map ring's depth and the section list itself.
+struct pgtg_snapshot {
+  int device = 0;
+  uint64_t slots = 0;
+  std::vector<StateSection> sec;  // ptr: the snapshot's own array; bytes: for `slots` envs
+  PgtgStateHeader shape{};        // nt .. car_slots and cfg_hash (the other fields unused)
+  int depth = 0;                  // queue_depth of the handle, 0 without the map queue
+  uint64_t device_bytes = 0, bytes_per_env = 0;
+};
+
+static void snapshot_shape(pgtg_handle* h, PgtgStateHeader* hd, int* depth) {
+  hd->nt = (uint32_t)h->hcfg.nt;
+  hd->car_cap = (uint32_t)h->hcfg.car_cap;
+  hd->plan_stride = (uint32_t)h->hcfg.plan_stride;
+  hd->max_spawners = (uint32_t)h->hcfg.max_spawners;
+  hd->vis_words = (uint32_t)h->hcfg.vis_words;
+  hd->qrec_dw = (uint32_t)h->hcfg.qrec_dw;
+  hd->car_slots = (uint32_t)h->hcfg.car_slots;
+  hd->cfg_hash = cfg_hash(h->hcfg);
+  *depth = h->S.qbuf ? queue_depth(h) : 0;
+}
+
+static uint64_t section_bytes(const StateSection& s, uint64_t n) {
+  return s.kind == kSecRows ? n * s.row : s.row * n * 4;
+}
+
+int pgtg_snapshot_create(pgtg_handle* h, uint64_t slots, pgtg_snapshot** out) {
+  if (!h || !out) return PGTG_E_INVALID;
+  if (slots == 0 || slots > 0xffffffffull) return fail(h, PGTG_E_INVALID, "pgtg_snapshot_create: slots outside [1, 2^32)");
+  HIPCHK(h, hipSetDevice(h->device));
+  pgtg_snapshot* s = new pgtg_snapshot;
+  s->device = h->device;
+  s->slots = slots;
+  snapshot_shape(h, &s->shape, &s->depth);
+  for (const auto& hs : state_sections(h)) {
+    if (hs.kind == kSecBatch) continue;
+    StateSection e = hs;
+    e.ptr = nullptr;
+    e.bytes = section_bytes(hs, slots);
+    hipError_t rc = hipMalloc(&e.ptr, e.bytes);
+    if (rc == hipSuccess) rc = hipMemsetAsync(e.ptr, 0, e.bytes, h->stream);
+    if (rc != hipSuccess) {
+      if (e.ptr) (void)hipFree(e.ptr);
+      pgtg_snapshot_destroy(s);
+      return fail(h, PGTG_E_DEVICE, std::string("pgtg_snapshot_create: ") + hipGetErrorString(rc));
+    }
+    s->sec.push_back(e);
+    s->device_bytes += e.bytes;
+    s->bytes_per_env += section_bytes(hs, 1);
+  }
+  if (s->sec.size() > (size_t)kMaxCopySections) {
+    pgtg_snapshot_destroy(s);
+    return fail(h, PGTG_E_UNSUPPORTED, "pgtg_snapshot_create: more state sections than the copy table holds");
+  }
+  *out = s;
+  return PGTG_OK;
+}
+
+int pgtg_snapshot_destroy(pgtg_snapshot* s) {
+  if (!s) return PGTG_OK;
+  (void)hipSetDevice(s->device);
+  for (auto& e : s->sec) (void)hipFree(e.ptr);  // (hipFree waits for the device: no copy is still running)
+  delete s;
+  return PGTG_OK;
+}
+
+int pgtg_snapshot_bytes(const pgtg_snapshot* s, uint64_t* device_bytes, uint64_t* bytes_per_env) {
+  if (!s) return PGTG_E_INVALID;
+  if (device_bytes) *device_bytes = s->device_bytes;
+  if (bytes_per_env) *bytes_per_env = s->bytes_per_env;
+  return PGTG_OK;
+}
+
+// The copy table of a save (to_snapshot) or a load, or why this handle may not use the snapshot.
+static int snapshot_table(pgtg_handle* h, const pgtg_snapshot* s, bool to_snapshot, const char* who, CopyTable* T) {
+  PgtgStateHeader hd{};
+  int depth = 0;
+  snapshot_shape(h, &hd, &depth);
+  const PgtgStateHeader& q = s->shape;
+  if (h->device != s->device) return fail(h, PGTG_E_INVALID, std::string(who) + ": the snapshot lives on another device");
+  if (hd.nt != q.nt || hd.car_cap != q.car_cap || hd.plan_stride != q.plan_stride || hd.max_spawners != q.max_spawners ||
+      hd.vis_words != q.vis_words || hd.qrec_dw != q.qrec_dw || hd.car_slots != q.car_slots)
+    return fail(h, PGTG_E_INVALID, std::string(who) + ": the snapshot was created from a handle of another shape");
+  if (hd.cfg_hash != q.cfg_hash)
+    return fail(h, PGTG_E_INVALID, std::string(who) + ": the snapshot was created from a handle of another configuration");
+  if (depth != s->depth)
+    return fail(h, PGTG_E_INVALID, std::string(who) + ": the snapshot was created from a handle with another map-queue step "
+                                                      "kernel (its rings hold another number of maps)");
+  memset(T, 0, sizeof *T);
+  uint32_t k = 0;
+  for (const auto& hs : state_sections(h)) {
+    if (hs.kind == kSecBatch) continue;
+    if (k >= s->sec.size() || s->sec[k].id != hs.id || s->sec[k].kind != hs.kind || s->sec[k].row != hs.row)
+      return fail(h, PGTG_E_INVALID, std::string(who) + ": section list mismatch");
+    CopySection& e = T->sec[k];
+    e.src = to_snapshot ? hs.ptr : s->sec[k].ptr;
+    e.dst = to_snapshot ? s->sec[k].ptr : hs.ptr;
+    e.src_n = to_snapshot ? h->n : s->slots;
+    e.dst_n = to_snapshot ? s->slots : h->n;
+    e.kind = hs.kind;
+    e.row = (uint32_t)hs.row;
+    e.unit = 4;
+    if (hs.kind == kSecRows) {
+      const uint64_t bits = (uint64_t)(uintptr_t)e.src | (uint64_t)(uintptr_t)e.dst | hs.row;
+      e.unit = 16;
+      while (bits & (e.unit - 1)) e.unit >>= 1;
+    }
+    k++;
+  }
+  if (k != s->sec.size()) return fail(h, PGTG_E_INVALID, std::string(who) + ": section list mismatch");
+  T->n_sections = k;
+  return PGTG_OK;
+}
+
+static int snapshot_copy(pgtg_handle* h, const pgtg_snapshot* s, bool to_snapshot, const char* who, const uint32_t* src_idx,
+                         const uint32_t* dst_idx, uint64_t count) {
+  if (!h || !s) return PGTG_E_INVALID;
+  CopyTable T;
+  if (int rc = snapshot_table(h, s, to_snapshot, who, &T)) return rc;
+  if (count > 0xffffffffull) return fail(h, PGTG_E_INVALID, std::string(who) + ": more than 2^32 - 1 pairs");
+  if (count == 0) return PGTG_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  // the map rings complete and the refill request lists empty (as before a dump): a saved ring is whole,
+  // and no request of the last step launch names a ring that a load is about to replace.  The loaded
+  // rings were saved whole, every other ring is whole now, and the lists stay empty (qctr zeroed by
+  // queue_fill) until the next step launch: nothing is left to zero after the copy.  The k_traffic
+  // work list is written and consumed inside one step launch, so none is pending either.
+  if (int rc = queue_fill(h)) return rc;
+  T.src_idx = src_idx;
+  T.dst_idx = dst_idx;
+  T.count = count;
+  if (!to_snapshot && h->ep.ret) {  // the episode accumulators are not state: a loaded env starts a new count
+    T.ep_ret = h->ep.ret;
+    T.ep_len = h->ep.len;
+  }
+  hipLaunchKernelGGL(k_state_copy, dim3((unsigned)((count + kCopyBlock - 1) / kCopyBlock)), dim3(kCopyBlock), 0, h->stream, T);
+  HIPCHK(h, hipGetLastError());
+  return PGTG_OK;
+}
+
+int pgtg_snapshot_save(pgtg_handle* h, pgtg_snapshot* s, const uint32_t* env_idx_dev, const uint32_t* slot_idx_dev,
+                       uint64_t count) {
+  return snapshot_copy(h, s, true, "pgtg_snapshot_save", env_idx_dev, slot_idx_dev, count);
+}
+
+int pgtg_snapshot_load(pgtg_handle* h, const pgtg_snapshot* s, const uint32_t* slot_idx_dev, const uint32_t* env_idx_dev,
+                       uint64_t count) {
+  return snapshot_copy(h, s, false, "pgtg_snapshot_load", slot_idx_dev, env_idx_dev, count);
 }
 
 // PGTGEnv.set_to_state (environment.py:1301-1342) for env `env`: position, velocity and flat tire,

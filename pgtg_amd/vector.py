@@ -35,6 +35,111 @@ def _check(rc: int, handle=None) -> None:
         raise _EXC.get(rc, RuntimeError)((msg or b"").decode() or f"pgtg error {rc}")
 
 
+def fork_indices(roots, copies: int):
+    """(slot_idx, env_idx) for Snapshot.load: root r goes into the envs r*copies .. r*copies+copies-1,
+    so roots 0 .. R-1 fill a batch of R*copies envs with `copies` clones each.  Pure torch (int64
+    tensors on the device of `roots`; a sequence gives CPU tensors)."""
+    import torch
+    r = torch.as_tensor(roots).to(torch.int64).reshape(-1)
+    copies = int(copies)
+    if copies < 1:
+        raise ValueError("copies must be at least 1")
+    slot_idx = r.repeat_interleave(copies)
+    env_idx = (r.unsqueeze(1) * copies + torch.arange(copies, dtype=torch.int64, device=r.device)).reshape(-1)
+    return slot_idx, env_idx
+
+
+class Snapshot:
+    """Device-resident copies of single envs' state (include/pgtg.h pgtg_snapshot_*): `slots` places,
+    each holding everything one env carries from one step to the next.  Made by PGTGVecEnv.snapshot();
+    usable with every PGTGVecEnv of the same configuration, car capacity and map-queue kernel on the
+    same device, whatever its batch size.  save and load are one kernel launch on the current stream
+    and do not synchronise; the snapshot is ordered with that stream."""
+
+    def __init__(self, env: "PGTGVecEnv", slots: int | None = None):
+        self._lib = env._lib
+        self.slots = int(env.num_envs if slots is None else slots)
+        self.device = env.device
+        s = C.c_void_p()
+        env._bind_stream()
+        _check(self._lib.pgtg_snapshot_create(env._h, C.c_uint64(max(self.slots, 0)), C.byref(s)), env._h)
+        self._s = s
+        total, per_env = C.c_uint64(), C.c_uint64()
+        _check(self._lib.pgtg_snapshot_bytes(s, C.byref(total), C.byref(per_env)), env._h)
+        self.nbytes, self.bytes_per_env = total.value, per_env.value
+        self._refs = ()
+
+    def _indices(self, a, b, na: int, nb: int, check: bool):
+        """The two index arrays of a call as int32 device tensors holding the uint32 bits (or None: the
+        identity), and the pair count.  a indexes a side of na places and is the source, b of nb."""
+        import torch
+        out = []
+        for x in (a, b):
+            if x is not None:
+                x = torch.as_tensor(x, device=self.device)
+                if x.numel() and (x.dtype.is_floating_point or x.dtype == torch.bool):
+                    raise ValueError("indices must be integers")
+                x = x.to(torch.int64).reshape(-1)
+            out.append(x)
+        a, b = out
+        if a is not None and b is not None and a.numel() != b.numel():
+            raise ValueError(f"{a.numel()} source indices for {b.numel()} destinations")
+        count = a.numel() if a is not None else b.numel() if b is not None else min(na, nb)
+        if check:  # (one device sync)
+            bad = False
+            for x, n in ((a, na), (b, nb)):
+                if x is None:
+                    bad = bad or count > n  # (the identity runs past this side)
+                elif x.numel():
+                    bad = bad or bool(((x < 0) | (x >= n)).any())
+            if bad:
+                raise ValueError(f"index outside the snapshot's {self.slots} slots or the batch")
+            if b is not None and torch.unique(b).numel() != b.numel():
+                raise ValueError("a destination appears more than once")
+        return [None if x is None else x.to(torch.int32).contiguous() for x in (a, b)], count
+
+    def _call(self, fn, env, src, dst, count):
+        if self._s is None:
+            raise RuntimeError("the snapshot is closed")
+        env._bind_stream()
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+        _check(fn(env._h, self._s, ptr(src), ptr(dst), C.c_uint64(count)), env._h)
+        self._refs = (src, dst)  # (the launch reads them)
+
+    def save(self, env: "PGTGVecEnv", env_idx=None, slot_idx=None) -> None:
+        """Env env_idx[k] of `env` into slot slot_idx[k].  Int tensors on the device or sequences; None
+        is the identity k -> k (both None: the first min(num_envs, slots) envs).  A pair with an index
+        outside its side is skipped; a slot named twice ends up unspecified."""
+        (src, dst), count = self._indices(env_idx, slot_idx, env.num_envs, self.slots, False)
+        self._call(self._lib.pgtg_snapshot_save, env, src, dst, count)
+
+    def load(self, env: "PGTGVecEnv", slot_idx=None, env_idx=None, observe: bool = True, check: bool = True) -> None:
+        """Slot slot_idx[k] into env env_idx[k] of `env`; a slot may be named many times (fork).
+        check=True verifies with torch ops that every index is in range and that no env is named twice,
+        and raises ValueError otherwise: this costs a device synchronisation.  With check=False an
+        out-of-range pair is skipped by the kernel, and an env named twice ends up with an unspecified
+        mix of its sources (memory-safe; nothing else is touched).  The loaded envs' running episode
+        return and length (enable_episode_stats) restart at zero.  Outputs are not state: observe=True
+        re-emits every env's observation into the bound tensors afterwards."""
+        (src, dst), count = self._indices(slot_idx, env_idx, self.slots, env.num_envs, check)
+        self._call(self._lib.pgtg_snapshot_load, env, src, dst, count)
+        env._seeded = True
+        if observe:
+            env.observe()
+
+    def close(self) -> None:
+        """Free the device arrays (waits for the device)."""
+        if getattr(self, "_s", None):
+            self._lib.pgtg_snapshot_destroy(self._s)
+            self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class PGTGVecEnv:
     def __init__(self, num_envs: int, map_path: str | None = None, *, device: int | None = None,
                  autoreset: bool = True, max_episode_steps: int | None = None, spec: EnvSpec | None = None,
@@ -98,6 +203,9 @@ class PGTGVecEnv:
             self._stream = s
 
     def close(self):
+        if getattr(self, "_scratch", None) is not None:  # (copy_envs / light_step)
+            self._scratch.close()
+            self._scratch = None
         if getattr(self, "_h", None):
             self._lib.pgtg_destroy(self._h)
             self._h = None
@@ -434,6 +542,69 @@ class PGTGVecEnv:
         self._seeded = True
         if observe:
             self.observe()
+
+    # -- device-resident snapshots: save, restore and fork single envs ---------------------------------
+    def snapshot(self, slots: int | None = None) -> Snapshot:
+        """A Snapshot of `slots` places (default num_envs) for this env and every other PGTGVecEnv of its
+        configuration on this device: snap.save(env, ...), snap.load(env, ...)."""
+        return Snapshot(self, slots)
+
+    def _scratch_snapshot(self, slots: int) -> Snapshot:
+        s = getattr(self, "_scratch", None)
+        if s is None or s.slots < slots:
+            if s is not None:
+                s.close()
+            s = self._scratch = Snapshot(self, slots)
+        return s
+
+    def copy_envs(self, src, dst, observe: bool = True, check: bool = True) -> None:
+        """Env src[k] into env dst[k] of this batch (a fork inside the batch), through a scratch snapshot:
+        every source is read before any destination is written, so `src` and `dst` may overlap (gather
+        semantics: dst[k] becomes what src[k] was before the call).  check / observe as in Snapshot.load."""
+        import torch
+        src = torch.as_tensor(src, device=self.device).reshape(-1)
+        if check and src.numel() and bool(((src < 0) | (src >= self.num_envs)).any()):
+            raise ValueError(f"source index outside the batch of {self.num_envs} envs")
+        snap = self._scratch_snapshot(max(1, src.numel()))
+        snap.save(self, src, None)
+        snap.load(self, torch.arange(src.numel(), device=self.device), dst, observe=observe, check=check)
+
+    def _bound_tensors(self) -> list:
+        """Every tensor a step launch writes: the outputs and whatever else is bound."""
+        ts = [self.obs_map, self.position, self.velocity, self.reward, self.terminated, self.truncated, self.braking,
+              self.cost, self.nsd, self.final_map, self.final_position, self.final_velocity, self.final_nsd]
+        for refs in ("_flat_refs", "_flat_scalar_refs", "_episode_refs"):
+            ts += list(getattr(self, refs, ()) or ())
+        return [t for t in ts if t is not None]
+
+    def light_step(self, actions) -> tuple[dict, Any, Any, Any]:
+        """The batch form of PGTGEnv.light_step (environment.py:1283-1299): what step(actions) would
+        return -- clones of (observation dict, reward, terminated, truncated) -- with every env's state
+        and every bound output tensor put back as they were.  All on the device: a save into a scratch
+        snapshot, the step, a load.  Not restored: the batch-wide counters() (the step is counted), and,
+        with episode statistics enabled, the running return and length of every env, which restart at zero
+        as after any load (the step itself is kept out of the statistics)."""
+        snap = self._scratch_snapshot(self.num_envs)
+        snap.save(self)
+        bound = self._bound_tensors()
+        kept = [t.clone() for t in bound]
+        stats = self._episode_refs
+        if stats:
+            self.disable_episode_stats()
+        try:
+            self.step_launch(actions)
+            m, pos, vel = self.obs_map.clone(), self.position.clone(), self.velocity.clone()
+            obs = {"position": pos, "velocity": vel, "map": {k: m[:, i] for i, k in enumerate(self.keys)}}
+            if self.nsd is not None:
+                obs["next_subgoal_direction"] = self.nsd.clone()
+            out = (obs, self.reward.clone(), self.terminated.clone(), self.truncated.clone())
+        finally:
+            snap.load(self, observe=False, check=False)
+            for t, k in zip(bound, kept):
+                t.copy_(k)
+            if stats:
+                self._bind_episode_ptrs(*stats)
+        return out
 
     def set_to_state(self, i: int, x: int, y: int, vx: int, vy: int, flat_tire: bool, cars=()):
         """PGTGEnv.set_to_state for env i (environment.py:1301-1342); cars = [(id, x, y, route, profile)]."""
