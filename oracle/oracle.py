@@ -63,6 +63,14 @@ class OrcPcg(C.Structure):
                 ("inc_lo", C.c_uint64), ("has32", C.c_int32), ("buf32", C.c_uint32)]
 
 
+class OrcTraceRec(C.Structure):
+    _fields_ = [("site", C.c_int32), ("n", C.c_uint32), ("ord", C.c_int32), ("buffered", C.c_int32),
+                ("car", C.c_int32), ("rejects", C.c_int32)]
+
+
+# sites of the rejection trace (pgtg_oracle.h ORC_SITE_*)
+SITES = ("other", "mapgen", "startgoal", "floyd", "shuffle", "init_route", "car_pass", "agent")
+
 _lib = None
 
 
@@ -74,8 +82,9 @@ def build() -> str:
 def lib():
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            build()
+        srcs = [os.path.join(HERE, f) for f in ("pgtg_oracle.c", "pgtg_oracle.h", "oracle_tables.h")]
+        if not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs):
+            build()  # missing, or left from an older tree (it would lack newer entry points)
         L = C.CDLL(LIB_PATH)
         L.orc_create.restype = C.c_void_p
         L.orc_create.argtypes = [C.POINTER(OrcConfig)]
@@ -114,8 +123,68 @@ def lib():
         L.orc_rollout_digest_tl.restype = C.c_int
         L.orc_rollout_digest_tl.argtypes = [C.POINTER(OrcConfig), C.c_int64, C.c_uint64, C.c_int, C.c_uint64, C.c_int,
                                             C.c_void_p, C.c_void_p]
+        _bind_trace(L)
         _lib = L
     return _lib
+
+
+def _bind_trace(L):
+    L.orc_get_traffic_reset.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.orc_trace_begin.restype = None
+    L.orc_trace_begin.argtypes = [C.POINTER(OrcTraceRec), C.c_int]
+    L.orc_trace_clear.restype = None
+    L.orc_trace_clear.argtypes = []
+    L.orc_trace_count.argtypes = []
+    L.orc_trace_end.argtypes = []
+
+
+def load(path: str):
+    """A second build of the oracle (tests/test_lemire_fixture.py's -DORC_NO_REJECT copy) with the
+    entry points the rejection fixture needs; the module's own library is left alone."""
+    L = C.CDLL(path)
+    L.orc_create.restype = C.c_void_p
+    L.orc_create.argtypes = [C.POINTER(OrcConfig)]
+    L.orc_destroy.argtypes = [C.c_void_p]
+    L.orc_reset.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(OrcOut)]
+    L.orc_step.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(OrcOut)]
+    L.orc_window.argtypes = [C.c_void_p]
+    L.orc_num_cars.argtypes = [C.c_void_p]
+    L.orc_get_cars.argtypes = [C.c_void_p, C.POINTER(OrcCar), C.c_int]
+    L.orc_last_error.restype = C.c_char_p
+    L.orc_last_error.argtypes = [C.c_void_p]
+    _bind_trace(L)
+    return L
+
+
+class Trace:
+    """Rejection trace of the calling thread's bounded draws: `with Trace() as t: ...; t.records()`
+    gives dicts {site, n, ord, buffered, car, rejects} for every draw that could reject (left < n),
+    rejects > 0 where it did.  clear() starts over (e.g. per reset or step)."""
+
+    def __init__(self, cap: int = 4096, L=None):
+        self._L = L or lib()
+        self._buf = (OrcTraceRec * cap)()
+        self._cap = cap
+
+    def __enter__(self):
+        self._L.orc_trace_begin(self._buf, self._cap)
+        return self
+
+    def __exit__(self, *exc):
+        self._L.orc_trace_end()
+
+    def clear(self):
+        self._L.orc_trace_clear()
+
+    def count(self) -> int:
+        return self._L.orc_trace_count()
+
+    def records(self) -> list[dict]:
+        n = self.count()
+        if n > self._cap:
+            raise RuntimeError(f"rejection trace overflow: {n} records, capacity {self._cap}")
+        return [{"site": SITES[r.site], "n": int(r.n), "ord": r.ord, "buffered": r.buffered, "car": r.car,
+                 "rejects": r.rejects} for r in self._buf[:n]]
 
 
 def config_from_spec(spec) -> OrcConfig:
@@ -308,6 +377,12 @@ class OracleEnv:
         sc = C.c_uint32()
         self._L.orc_get_misc(self._h, C.byref(ph), C.byref(ft), C.byref(nid), C.byref(sc))
         return {"phase": ph.value, "flat_tire": ft.value, "next_car_id": nid.value, "spawn_counter": sc.value}
+
+    def traffic_reset(self) -> tuple[int, int]:
+        """(np, k) of the last reset's initial traffic: spawnable squares and cars chosen among them."""
+        np_, k = C.c_int32(), C.c_int32()
+        self._L.orc_get_traffic_reset(self._h, C.byref(np_), C.byref(k))
+        return np_.value, k.value
 
     def set_agent(self, x, y, vx=None, vy=None):
         o = self.out

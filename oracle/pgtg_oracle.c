@@ -64,7 +64,8 @@ void orc_seed_seq_state(const uint32_t* entropy, int n, uint32_t out[8]) {
 
 static const u128 PCG_MULT = (((u128)0x2360ED051FC65DA4ull) << 64) | (u128)0x4385DF649FCCF645ull;
 
-typedef struct { u128 state, inc; int has32; uint32_t buf32; } pcg_t;
+/* site / ord / car: where a stream's bounded draws are made, for the rejection trace (below) only */
+typedef struct { u128 state, inc; int has32; uint32_t buf32; int site, ord, car; } pcg_t;
 
 static void pcg_step(pcg_t* g) { g->state = g->state * PCG_MULT + g->inc; }
 
@@ -117,18 +118,55 @@ static void pcg_from_seed(pcg_t* g, uint64_t seed, int has_key, uint32_t key) {
   pcg_step(g);
   g->has32 = 0;
   g->buf32 = 0;
+  g->site = ORC_SITE_OTHER;
+  g->ord = 0;
+  g->car = -1;
+}
+
+/* Rejection trace (tests and tools/find_rejection_seeds.py): while a buffer is installed on the
+ * calling thread, every bounded draw that could reject (left < n) is recorded, with the number of
+ * halves it did reject (left < 2^32 mod n).  Only that rare branch touches the trace, so nothing
+ * else changes with or without it. */
+static __thread struct { orc_trace_rec* buf; int cap, n; } g_trace;
+
+void orc_trace_begin(orc_trace_rec* buf, int cap) {
+  g_trace.buf = buf;
+  g_trace.cap = cap;
+  g_trace.n = 0;
+}
+void orc_trace_clear(void) { g_trace.n = 0; }
+int orc_trace_count(void) { return g_trace.n; }
+int orc_trace_end(void) {
+  int n = g_trace.n;
+  g_trace.buf = NULL;
+  g_trace.cap = g_trace.n = 0;
+  return n;
+}
+static void trace_put(const pcg_t* g, uint32_t n, int buffered, int rejects) {
+  if (!g_trace.buf) return;
+  if (g_trace.n < g_trace.cap)
+    g_trace.buf[g_trace.n] = (orc_trace_rec){g->site, n, g->ord - 1, buffered, g->car, rejects};
+  g_trace.n++;
 }
 
 static uint32_t lemire32(pcg_t* g, uint32_t rng) { /* result in [0, rng] */
   uint32_t excl = rng + 1;
+  int buffered = g->has32;
   uint64_t m = (uint64_t)pcg_next32(g) * excl;
   uint32_t left = (uint32_t)m;
   if (left < excl) {
     uint32_t thr = (0xffffffffu - rng) % excl;
+    int rejects = 0;
+#ifdef ORC_NO_REJECT /* tests/test_lemire_fixture.py only: the wrong generator the fixture must tell apart */
+    rejects = left < thr;
+#else
     while (left < thr) {
       m = (uint64_t)pcg_next32(g) * excl;
       left = (uint32_t)m;
+      rejects++;
     }
+#endif
+    trace_put(g, excl, buffered, rejects);
   }
   return (uint32_t)(m >> 32);
 }
@@ -136,6 +174,7 @@ static uint32_t lemire32(pcg_t* g, uint32_t rng) { /* result in [0, rng] */
 /* Generator.integers(lo, hi) (int64, endpoint False) == Generator.choice(n) index */
 static int64_t gen_integers(pcg_t* g, int64_t lo, int64_t hi) {
   uint64_t rng = (uint64_t)(hi - lo - 1);
+  g->ord++; /* the draw's ordinal at its site, whether or not it takes a half */
   if (rng == 0) return lo;
   if (rng == 0xffffffffull) return lo + pcg_next32(g);
   return lo + lemire32(g, (uint32_t)rng);
@@ -160,7 +199,11 @@ static int gen_choice_p(pcg_t* g, const double* p, int n) {
 /* Generator.choice(pop, size=k, replace=False) for pop <= 10000: Floyd, then _shuffle_int */
 static void gen_choice_noreplace(pcg_t* g, int64_t pop, int64_t k, int64_t* out) {
   unsigned char* seen = (unsigned char*)calloc((size_t)pop + 1, 1);
+  const int site0 = g->site, ord0 = g->ord;
+  /* trace ordinal d: Floyd's draws are d = 0 .. k-1, the shuffle's d = k .. 2k-2, in stream order */
+  g->site = ORC_SITE_FLOYD;
   for (int64_t j = pop - k; j < pop; j++) {
+    g->ord = (int)(j - pop + k);
     int64_t val = gen_integers(g, 0, j + 1);
     if (!seen[val]) {
       seen[val] = 1;
@@ -171,12 +214,16 @@ static void gen_choice_noreplace(pcg_t* g, int64_t pop, int64_t k, int64_t* out)
     }
   }
   free(seen);
+  g->site = ORC_SITE_SHUFFLE;
   for (int64_t i = k - 1; i >= 1; i--) {
+    g->ord = (int)(2 * k - 1 - i);
     int64_t j = gen_integers(g, 0, i + 1); /* _shuffle_int: random_bounded_uint64(0, i) (Lemire) */
     int64_t t = out[j];
     out[j] = out[i];
     out[i] = t;
   }
+  g->site = site0;
+  g->ord = ord0;
 }
 
 /* exported wrappers (known-answer tests against numpy) */
@@ -193,6 +240,9 @@ static void from_pub(const orc_pcg64* o, pcg_t* g) {
   g->inc = ((u128)o->inc_hi << 64) | o->inc_lo;
   g->has32 = o->has32;
   g->buf32 = o->buf32;
+  g->site = ORC_SITE_OTHER;
+  g->ord = 0;
+  g->car = -1;
 }
 void orc_pcg64_from_seed(uint64_t seed, uint32_t key, int has_key, orc_pcg64* o) {
   pcg_t g;
@@ -282,6 +332,7 @@ struct orc_env {
   car_t* cars;
   int ncars, capcars, next_car_id;
   double profile_p[5];
+  int last_np, last_k; /* population and sample size of the last reset's choice of car squares */
 };
 
 static int fail(orc_env* e, const char* m) {
@@ -486,7 +537,10 @@ static int generate_map(orc_env* e) {
   int w = c->width, h = c->height;
   pcg_t* r = &e->map_rng;
   int s[3], g3[3], sl, gl;
+  r->site = ORC_SITE_STARTGOAL;
   choose_start_goal(e, r, s, &sl, g3, &gl);
+  r->site = ORC_SITE_MAPGEN;
+  r->ord = 0;
   /* generate_map_graph, pgtg/map_generator.py:192-266 */
   graph_t* Gp = (graph_t*)malloc(sizeof(graph_t));
 #define G (*Gp)
@@ -808,8 +862,11 @@ static int select_profile(orc_env* e) { return gen_choice_p(&e->car_rng, e->prof
 static int create_initial_traffic(orc_env* e) {
   int np = e->n_spawnable;
   int ncars = (int)((double)np * e->cfg.traffic_density);
+  e->last_np = np;
+  e->last_k = 0;
   if (ncars > 0 && np > 0) {
     int k = ncars < np ? ncars : np;
+    e->last_k = k;
     int64_t* idx = (int64_t*)malloc(sizeof(int64_t) * (size_t)k);
     gen_choice_noreplace(&e->car_rng, np, k, idx);
     for (int i = 0; i < k; i++) {
@@ -821,9 +878,13 @@ static int create_initial_traffic(orc_env* e) {
         return fail(e, "a car was spawned on a field where no car lane was found");
       }
       int prof = select_profile(e);
+      e->car_rng.site = ORC_SITE_INIT_ROUTE; /* ordinal = car index */
+      e->car_rng.ord = e->car_rng.car = i;
       int lane = rl[gen_integers(&e->car_rng, 0, nr)];
       push_car(e, (car_t){e->next_car_id++, x, y, lane_route_id(lane), prof, 0, 0});
     }
+    e->car_rng.site = ORC_SITE_CAR_PASS;
+    e->car_rng.car = -1;
     free(idx);
   }
   return 0;
@@ -933,6 +994,7 @@ static int move_cars(orc_env* e) { /* :1121-1127 */
   for (int k = 0; k < n0; k++) {
     int i = 0;
     while (e->cars[i].id != ids[k]) i++; /* the snapshot's car object */
+    e->car_rng.car = ids[k];
     int nx, ny, nr;
     int r = next_car_position(e, &e->cars[i], &nx, &ny, &nr);
     if (r == -2) {
@@ -1166,6 +1228,8 @@ int orc_reset(orc_env* e, int64_t seed, uint8_t* obs, orc_out* out) {
   if (compile_map(e)) return -1;
   e->ind_reward = c->sum_subgoals_reward / (double)e->num_subgoals;
   if (e->n_starters == 0) return fail(e, "no start squares");
+  e->map_rng.site = e->ice_rng.site = ORC_SITE_AGENT;
+  e->map_rng.ord = 0;
   int code = e->starters[gen_integers(&e->map_rng, 0, e->n_starters)];
   e->px = code / e->H;
   e->py = code % e->H;
@@ -1230,6 +1294,8 @@ int orc_step(orc_env* e, int32_t action, uint8_t* obs, orc_out* out) {
   if (action < 0 || action > 8) return fail(e, "invalid action");
   e->phase = (e->phase + 1) % (c->phase_dur[0] + c->phase_dur[1] + c->phase_dur[2]);
   int ax = ACC[action][0], ay = ACC[action][1];
+  e->car_rng.site = ORC_SITE_CAR_PASS; /* trace ordinals count from the step's first bounded draw */
+  e->car_rng.ord = e->ice_rng.ord = 0;
   if (move_cars(e)) return -1;
   double reward = 0.0, perf = 0.0, cost = 0.0;
   int cx = e->px, cy = e->py;
@@ -1344,6 +1410,11 @@ int orc_get_misc(const orc_env* e, int32_t* phase, int32_t* flat_tire, int32_t* 
   *flat_tire = e->flat_tire;
   *next_car_id = e->next_car_id;
   *spawn_counter = e->spawn_counter;
+  return 0;
+}
+int orc_get_traffic_reset(const orc_env* e, int32_t* np, int32_t* k) {
+  *np = e->last_np;
+  *k = e->last_k;
   return 0;
 }
 int orc_set_agent(orc_env* e, int32_t x, int32_t y, int32_t vx, int32_t vy) {
