@@ -16,6 +16,8 @@
  *   pgtg_get_counters <- (new) device-side env-step / episode counters
  *   pgtg_set_episode_stats / pgtg_episode_summary <- (new, no reference function) the VecMonitor
  *                        wrapper the reference's caller puts around the vector env  pgtg/train.py:55
+ *   pgtg_gae          <- (new, no reference function) RolloutBuffer.compute_returns_and_advantage of the
+ *                        PPO the reference's caller trains                 pgtg/train.py:61-74
  *   pgtg_snapshot_*   <- copy.deepcopy(env) / env.clone() for single envs of the batch, on the device
  *                        environment.py:1283-1299, pgtg/evaluator.py:98-110
  *
@@ -302,6 +304,34 @@ int pgtg_set_episode_stats(pgtg_handle* h, float* ep_return_dev, int32_t* ep_len
  * without atomics and combined here in row order: the same bits on any device and for any step kernel).
  * Synchronises.  PGTG_E_INVALID if statistics were never bound. */
 int pgtg_episode_summary(pgtg_handle* h, PgtgEpisodeSummary* out, int32_t reset);
+/* Generalised advantage estimation over a device-resident rollout of N envs and T steps (new; no
+ * reference function: it replaces RolloutBuffer.compute_returns_and_advantage of the PPO of
+ * pgtg/train.py:61-74, and the time-limit bootstrap reward += gamma * V(terminal_observation) that its
+ * collect_rollouts applies to truncated envs).  One launch of k_gae, one lane per env, float32 and
+ * without fused multiply-add, operation for operation what SB3 computes in numpy:
+ *   g = (float)gamma;  gl = (float)(gamma * gae_lambda)  (the product in double);  last = 0;  t = T-1 .. 0:
+ *   r     = truncated_only[t][e] ? rewards[t][e] + g * terminal_values[t][e] : rewards[t][e]
+ *   nnt   = 1.0f - (float)(dones[t+1][e] != 0)
+ *   nv    = t == T-1 ? last_values[e] : values[t+1][e]
+ *   delta = (r + (g * nv) * nnt) - values[t][e]
+ *   last  = delta + (gl * nnt) * last
+ *   advantages[t][e] = last;  returns[t][e] = last + values[t][e]
+ * All pointers are device pointers.  The handle is used for its device, stream and error string only: n
+ * need not be its batch size.  steps == 0, a NULL required pointer, only one of truncated_only /
+ * terminal_values, or a non-finite gamma or gae_lambda: PGTG_E_INVALID with a message, nothing is
+ * launched.  n == 0 is a no-op.  Asynchronous on the handle's stream. */
+typedef struct {
+  uint64_t n, steps;              /* N envs, T >= 1 rows; every [T][N] array row-contiguous with pitch N */
+  double gamma, gae_lambda;
+  const float*   rewards;         /* [T][N] raw float32 rewards (k_flatten's scalar) */
+  const float*   values;          /* [T][N] */
+  const uint8_t* dones;           /* [T+1][N]: row t = episode_starts of step t, row T = dones after the last step */
+  const uint8_t* truncated_only;  /* [T][N]; NULL together with terminal_values = no bootstrap */
+  const float*   terminal_values; /* [T][N]; read ONLY where truncated_only != 0 */
+  const float*   last_values;     /* [N] */
+  float* advantages; float* returns;   /* [T][N] */
+} PgtgGae;
+int pgtg_gae(pgtg_handle* h, const PgtgGae* a);
 /* Re-emit the observation of every env into the bound outputs (after set_agent/add_car). */
 int pgtg_observe(pgtg_handle* h);
 /* Per-env uint64 digest of the car list into out_dev[N] (device; parity tests: the car term of

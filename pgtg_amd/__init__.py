@@ -4,6 +4,7 @@ Drop-in for the reference's hot path (Inuri04/pgtg `PGTGEnv.step/reset`, registe
   PGTGVecEnv  -- N independent episodes in lockstep on one GPU (HIP kernels via include/pgtg.h)
   PGTGEnv     -- single-env Gymnasium-style facade with the reference's constructor and returns
   Snapshot    -- single envs of a batch saved, restored and forked on the device (PGTGVecEnv.snapshot)
+  Rollout     -- PPO rollout buffer on the device with a fused GAE kernel (PGTGVecEnv.rollout)
 """
 from .config import EnvSpec, make_spec  # noqa: F401
 
@@ -14,6 +15,9 @@ def __getattr__(name):
     if name in ("PGTGVecEnv", "Snapshot", "fork_indices"):  # (device-resident snapshots of single envs)
         from . import vector
         return getattr(vector, name)
+    if name == "Rollout":
+        from .rollout import Rollout
+        return Rollout
     if name == "PGTGEnv":
         from .env import PGTGEnv
         return PGTGEnv

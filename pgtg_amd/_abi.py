@@ -33,7 +33,7 @@ EXPORTED = [
     "pgtg_error_count", "pgtg_window", "pgtg_num_envs", "pgtg_launch_info", "pgtg_occupancy", "pgtg_step_kernel", "pgtg_last_error", "pgtg_enable_timing",
     "pgtg_timing_read", "pgtg_measure_hbm", "pgtg_state_size", "pgtg_dump_state", "pgtg_load_state",
     "pgtg_set_to_state", "pgtg_car_digest", "pgtg_get_queue_maps", "pgtg_get_queue_overflow", "pgtg_set_flat_outputs", "pgtg_set_flat_scalars",
-    "pgtg_set_episode_stats", "pgtg_episode_summary",
+    "pgtg_set_episode_stats", "pgtg_episode_summary", "pgtg_gae",
     "pgtg_snapshot_create", "pgtg_snapshot_destroy", "pgtg_snapshot_bytes", "pgtg_snapshot_save", "pgtg_snapshot_load",
 ]
 
@@ -95,6 +95,12 @@ class PgtgEpisodeSummary(C.Structure):
                 ("return_min", C.c_float), ("return_max", C.c_float)]
 
 
+class PgtgGae(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("steps", C.c_uint64), ("gamma", C.c_double), ("gae_lambda", C.c_double)] + [
+        (n, C.c_void_p) for n in ("rewards", "values", "dones", "truncated_only", "terminal_values", "last_values",
+                                  "advantages", "returns")]
+
+
 _lib = None
 
 
@@ -143,6 +149,7 @@ def lib():
         "pgtg_set_flat_scalars": ([vp, vp, vp, vp], C.c_int),
         "pgtg_set_episode_stats": ([vp, vp, vp], C.c_int),
         "pgtg_episode_summary": ([vp, C.POINTER(PgtgEpisodeSummary), i32], C.c_int),
+        "pgtg_gae": ([vp, C.POINTER(PgtgGae)], C.c_int),
         "pgtg_snapshot_create": ([vp, u64, C.POINTER(vp)], C.c_int),
         "pgtg_snapshot_destroy": ([vp], C.c_int),
         "pgtg_snapshot_bytes": ([vp, C.POINTER(u64), C.POINTER(u64)], C.c_int),

@@ -27,6 +27,7 @@
 
 #include "pgtg_device.h"
 #include "pgtg_episode.h"
+#include "pgtg_rollout.h"
 #include "pgtg_snapshot.h"
 
 namespace pgtg {
@@ -6240,6 +6241,41 @@ int pgtg_episode_summary(pgtg_handle* h, PgtgEpisodeSummary* out, int32_t reset)
     HIPCHK(h, hipMemsetAsync(h->ep.rows, 0, rows.size() * sizeof(PgtgEpisodeSummary), h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
+  return PGTG_OK;
+}
+
+// GAE over a rollout (pgtg_rollout.h): the handle gives the device, the stream and the error string
+int pgtg_gae(pgtg_handle* h, const PgtgGae* a) {
+  if (!h) return PGTG_E_INVALID;
+  if (!a) return fail(h, PGTG_E_INVALID, "pgtg_gae: no arguments");
+  if (a->steps == 0) return fail(h, PGTG_E_INVALID, "pgtg_gae: steps must be at least 1");
+  if (!a->rewards || !a->values || !a->dones || !a->last_values || !a->advantages || !a->returns)
+    return fail(h, PGTG_E_INVALID, "pgtg_gae: rewards, values, dones, last_values, advantages and returns are required");
+  if ((a->truncated_only == nullptr) != (a->terminal_values == nullptr))
+    return fail(h, PGTG_E_INVALID, "pgtg_gae: truncated_only and terminal_values: both or neither");
+  if (!std::isfinite(a->gamma) || !std::isfinite(a->gae_lambda))
+    return fail(h, PGTG_E_INVALID, "pgtg_gae: gamma and gae_lambda must be finite");
+  if (a->n == 0) return PGTG_OK;
+  const uint64_t grid = (a->n + kGaeBlock - 1) / kGaeBlock;
+  if (grid > 0x7fffffffull || a->steps > 0x7fffffffull || a->steps + 1 > UINT64_MAX / 4 / a->n)
+    return fail(h, PGTG_E_UNSUPPORTED, "pgtg_gae: the rollout is too large for one launch");
+  GaeArgs g;
+  g.rew = a->rewards;
+  g.val = a->values;
+  g.dones = a->dones;
+  g.tonly = a->truncated_only;
+  g.tval = a->terminal_values;
+  g.last_values = a->last_values;
+  g.adv = a->advantages;
+  g.ret = a->returns;
+  g.n = a->n;
+  g.steps = a->steps;
+  g.g = (float)a->gamma;
+  g.gl = (float)(a->gamma * a->gae_lambda);  // (SB3: the product in double, rounded once)
+  HIPCHK(h, hipSetDevice(h->device));
+  if (g.tonly) hipLaunchKernelGGL(k_gae<true>, dim3((unsigned)grid), dim3(kGaeBlock), 0, h->stream, g);
+  else hipLaunchKernelGGL(k_gae<false>, dim3((unsigned)grid), dim3(kGaeBlock), 0, h->stream, g);
+  HIPCHK(h, hipGetLastError());
   return PGTG_OK;
 }
 

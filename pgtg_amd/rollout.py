@@ -1,0 +1,239 @@
+"""Device-resident PPO rollout buffer: SB3's `RolloutBuffer` for the batch (the PPO of pgtg/train.py:61-74).
+
+`PGTGVecEnv.rollout(n_steps, gamma, gae_lambda, obs_dtype)` gives a `Rollout`: the storage of one rollout
+of T = n_steps steps of all N envs, on the env's GPU.  Recording costs nothing beyond the step: every
+step's flattened observation, float32 reward, done and truncated-only flags are written by the step's own
+k_flatten pass straight into the rollout's rows (the handle's flat outputs are rebound to row t before each
+launch), and the terminal observations of the finished envs into `terminal_obs`.  `finish()` is one launch
+of the HIP kernel k_gae (include/pgtg.h pgtg_gae): the time-limit bootstrap and the backward GAE scan of
+`RolloutBuffer.compute_returns_and_advantage`.  `get()` hands out minibatches in SB3's sample order.
+
+    ro = env.rollout(128)
+    obs = ro.begin()
+    for t in range(128):
+        actions, values, log_probs = policy(obs)
+        obs, rewards, dones = ro.step(actions, values, log_probs)
+        ro.set_terminal_values(value_net(ro.terminal_obs))      # valid on the truncated rows
+    ro.finish(value_net(obs))
+    for obs_b, act_b, val_b, logp_b, adv_b, ret_b in ro.get(batch_size=4096): ...
+
+While a Rollout records, it owns the handle's flat bindings (set_flat_outputs / set_flat_scalars): bind
+nothing else to them until `close()`.
+
+`gae_reference` restates SB3's numpy loop (SB3 is not a dependency; the restatement is the yardstick of the
+tests, as the flatten layout's and the episode statistics' are).
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+from . import _abi
+from .flat import check_flattenable, flat_dim
+
+
+def sample_index(s, n_steps: int):
+    """(env, step) of flat sample index s: SB3's swap_and_flatten turns [T, N] into [N * T] with the
+    step running fastest, so s = env * T + step.  Works on ints, numpy arrays and tensors."""
+    return s // n_steps, s % n_steps
+
+
+def gae_reference(rewards, values, dones, truncated_only, terminal_values, last_values, gamma, gae_lambda):
+    """SB3's arithmetic in numpy float32 on host arrays: the time-limit bootstrap of collect_rollouts,
+    rewards[mask] += gamma * terminal_values[mask], then compute_returns_and_advantage.  rewards, values
+    [T, N]; dones [T + 1, N] (row t = episode_starts of step t, row T = dones after the last step);
+    truncated_only, terminal_values [T, N] or both None; last_values [N].  Returns (advantages, returns)."""
+    import numpy as np
+    rewards = np.array(rewards, dtype=np.float32)  # (a copy: the bootstrap is applied in place)
+    values = np.asarray(values, dtype=np.float32)
+    dones = np.asarray(dones)
+    last_values = np.asarray(last_values, dtype=np.float32)
+    gamma, gae_lambda = float(gamma), float(gae_lambda)
+    T = rewards.shape[0]
+    if truncated_only is not None:
+        mask = np.asarray(truncated_only) != 0
+        rewards[mask] += gamma * np.asarray(terminal_values, dtype=np.float32)[mask]
+    advantages = np.zeros_like(rewards)
+    last_gae_lam = 0
+    for step in reversed(range(T)):
+        next_non_terminal = 1.0 - (dones[step + 1] != 0).astype(np.float32)
+        next_values = last_values if step == T - 1 else values[step + 1]
+        delta = rewards[step] + gamma * next_values * next_non_terminal - values[step]
+        last_gae_lam = delta + gamma * gae_lambda * next_non_terminal * last_gae_lam
+        advantages[step] = last_gae_lam
+    return advantages, advantages + values
+
+
+class Rollout:
+    """One rollout of `n_steps` steps of every env of `env`, resident on its device (see the module text).
+
+    Tensors (T = n_steps, N = env.num_envs, D = the flat observation's length):
+      obs [T+1, N, D] int8 or float32 (row t: the observation step t acted on; row T: the next rollout's
+      first; rows are padded to 16 bytes, so obs[t] is contiguous and obs as a whole need not be),
+      actions [T, N] uint8, rewards [T, N] float32, dones [T+1, N] bool (row t = episode_starts of step t),
+      truncated_only [T, N] bool, values / log_probs / terminal_values / advantages / returns [T, N]
+      float32, terminal_obs [N, D] (the last step's terminal observations, valid on its finished envs)."""
+
+    def __init__(self, env, n_steps: int, gamma: float = 0.99, gae_lambda: float = 0.95, obs_dtype=None):
+        import torch
+        obs_dtype = torch.int8 if obs_dtype is None else obs_dtype
+        if isinstance(obs_dtype, str):
+            obs_dtype = getattr(torch, obs_dtype)
+        if int(n_steps) < 1:
+            raise ValueError("n_steps must be at least 1")
+        if not env.autoreset:
+            raise ValueError("a rollout needs autoreset=True (a finished env restarts in the same step)")
+        if obs_dtype not in (torch.int8, torch.float32):
+            raise ValueError("obs_dtype: torch.int8 or torch.float32")
+        try:
+            check_flattenable(env.spec)
+        except IndexError as e:
+            raise ValueError(str(e)) from None
+        self.env = env
+        self.n_steps = T = int(n_steps)
+        self.num_envs = N = env.num_envs
+        self.obs_dim = D = flat_dim(env.spec)
+        self.gamma, self.gae_lambda = float(gamma), float(gae_lambda)
+        self.device = dev = env.device
+        self._dtype_code = 0 if obs_dtype == torch.float32 else 1
+        # k_flatten wants 16-byte aligned [N, D] buffers: each obs row starts on a multiple of 16 bytes
+        item = torch.empty((), dtype=obs_dtype).element_size()
+        pitch = (N * D * item + 15) // 16 * 16 // item
+        self._obs_store = torch.zeros((T + 1) * pitch, dtype=obs_dtype, device=dev)
+        self.obs = self._obs_store.as_strided((T + 1, N, D), (pitch, D, 1))
+        self.terminal_obs = torch.zeros((N, D), dtype=obs_dtype, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.actions = torch.zeros((T, N), dtype=torch.uint8, device=dev)
+        self.rewards = torch.zeros((T, N), **f32)
+        self.dones = torch.zeros((T + 1, N), dtype=torch.bool, device=dev)
+        self.truncated_only = torch.zeros((T, N), dtype=torch.bool, device=dev)
+        self.values = torch.zeros((T, N), **f32)
+        self.log_probs = torch.zeros((T, N), **f32)
+        self.terminal_values = torch.zeros((T, N), **f32)
+        self.advantages = torch.zeros((T, N), **f32)
+        self.returns = torch.zeros((T, N), **f32)
+        self.t = 0
+        self._started = False  # the env has been reset into obs[0]
+        self._finished = False
+        self._last_values = None
+
+    @property
+    def nbytes(self) -> int:
+        """Device bytes the rollout holds."""
+        ts = (self._obs_store, self.terminal_obs, self.actions, self.rewards, self.dones, self.truncated_only,
+              self.values, self.log_probs, self.terminal_values, self.advantages, self.returns)
+        return sum(t.numel() * t.element_size() for t in ts)
+
+    # -- recording -------------------------------------------------------------------------------
+    def reset(self) -> None:
+        """Have the next begin() reset the env again (a new run, not the continuation of the last rollout)."""
+        self._started = False
+
+    def begin(self, seed=None):
+        """Start a rollout and return obs[0].  The first call (and the first after reset(), and any call
+        with a seed) resets the env with its observation written into obs[0], and sets dones[0] = 1: every
+        env starts an episode, SB3's _last_episode_starts.  A later call continues where the last rollout
+        ended: row T of obs and dones becomes row 0."""
+        env, T = self.env, self.n_steps
+        if not self._started or seed is not None:
+            env.set_flat_scalars(None, None, None)  # (the reset's observation pass writes no step scalars)
+            env.set_flat_outputs(self.obs[0], self.terminal_obs)
+            env.reset(seed=seed)
+            self.dones[0].fill_(True)
+            self._started = True
+        else:
+            self.obs[0].copy_(self.obs[T])
+            self.dones[0].copy_(self.dones[T])
+        self.terminal_values.zero_()  # (rows set_terminal_values is not called for stay zero)
+        self.t = 0
+        self._finished = False
+        return self.obs[0]
+
+    @staticmethod
+    def _into(row, src) -> None:
+        if src is not None and not (src.data_ptr() == row.data_ptr() and src.dtype == row.dtype
+                                    and src.shape == row.shape and src.is_contiguous()):
+            row.copy_(src.reshape(row.shape))
+
+    def step(self, actions, values=None, log_probs=None):
+        """One tick of every env from `actions` ([N] device tensor), recorded as step t: the step's
+        kernels write obs[t+1], rewards[t], dones[t+1], truncated_only[t] and terminal_obs themselves.
+        Launch-free beyond the tick only for uint8 actions that ARE the row (ro.actions[t]); another uint8
+        tensor costs one copy into the row, and any other integer dtype a few torch kernels more (every
+        value outside Discrete(9) becomes the invalid code 255, as in PGTGSB3VecEnv.step_async; the step
+        kernel records it per env, see PGTGVecEnv.error_count).  values / log_probs ([N]) are copied into
+        their rows unless they are the rows (ro.values[t], ro.log_probs[t]): a policy that writes into the
+        rows adds nothing.  Returns views (obs[t+1], rewards[t], dones[t+1])."""
+        import torch
+        t, env = self.t, self.env
+        if not self._started:
+            raise RuntimeError("begin() first")
+        if t >= self.n_steps:
+            raise RuntimeError(f"the rollout is full ({self.n_steps} steps): finish() and begin() again")
+        a = self.actions[t]
+        if actions.dtype != torch.uint8:  # every value outside Discrete(9) becomes the invalid code 255
+            actions = actions.to(torch.int64)
+            actions = torch.where((actions < 0) | (actions > 8), torch.full_like(actions, 255), actions)
+        self._into(a, actions)
+        self._into(self.values[t], values)
+        self._into(self.log_probs[t], log_probs)
+        env._bind_flat_ptrs(self.obs[t + 1], self.terminal_obs, self._dtype_code)
+        env._bind_flat_scalar_ptrs(self.rewards[t], self.dones[t + 1], self.truncated_only[t])
+        env.step_actions(a)
+        self.t = t + 1
+        return self.obs[t + 1], self.rewards[t], self.dones[t + 1]
+
+    def set_terminal_values(self, v) -> None:
+        """V(terminal_obs) of the step just taken, all N rows (used on the truncated-only ones):
+        terminal_values[t-1].  Not called: the row stays zero (no bootstrap)."""
+        if self.t < 1:
+            raise RuntimeError("no step has been taken")
+        self._into(self.terminal_values[self.t - 1], v)
+
+    def finish(self, last_values) -> None:
+        """advantages and returns of the whole rollout in one launch of k_gae; last_values = V(obs[T])."""
+        import torch
+        env, T, N = self.env, self.n_steps, self.num_envs
+        if self.t != T:
+            raise RuntimeError(f"finish() after {self.t} of {T} steps")
+        lv = last_values.to(device=self.device, dtype=torch.float32).reshape(N).contiguous()
+        self._last_values = lv  # (the launch reads it)
+        p = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
+        g = _abi.PgtgGae(n=N, steps=T, gamma=self.gamma, gae_lambda=self.gae_lambda, rewards=p(self.rewards),
+                         values=p(self.values), dones=p(self.dones), truncated_only=p(self.truncated_only),
+                         terminal_values=p(self.terminal_values), last_values=p(lv), advantages=p(self.advantages),
+                         returns=p(self.returns))
+        env._bind_stream()
+        rc = env._lib.pgtg_gae(env._h, C.byref(g))
+        if rc != _abi.PGTG_OK:
+            from .vector import _check
+            _check(rc, env._h)
+        self._finished = True
+
+    # -- minibatches ---------------------------------------------------------------------------
+    def get(self, batch_size: int | None = None, indices=None):
+        """Minibatches (obs float32 [B, D], actions int64 [B], values, log_probs, advantages, returns [B])
+        of the finished rollout.  Sample s is (env, step) = sample_index(s, T), SB3's swap_and_flatten
+        order, so SB3's permutation gives SB3's minibatches; indices=None draws torch.randperm on the
+        device; batch_size=None gives one batch of everything.  Torch indexing, no kernel of this library."""
+        import torch
+        if not self._finished:
+            raise RuntimeError("finish() first")
+        T, total = self.n_steps, self.n_steps * self.num_envs
+        if indices is None:
+            indices = torch.randperm(total, device=self.device)
+        idx = torch.as_tensor(indices, device=self.device).to(torch.int64).reshape(-1)
+        bs = idx.numel() if batch_size is None else int(batch_size)
+        if bs < 1:
+            raise ValueError("batch_size must be at least 1")
+        for lo in range(0, idx.numel(), bs):
+            e, t = sample_index(idx[lo:lo + bs], T)
+            yield (self.obs[t, e].to(torch.float32), self.actions[t, e].to(torch.int64), self.values[t, e],
+                   self.log_probs[t, e], self.advantages[t, e], self.returns[t, e])
+
+    def close(self) -> None:
+        """Unbind the flat rows and scalars from the handle (the tensors stay valid)."""
+        env = self.env
+        if env is not None and getattr(env, "_h", None):
+            env.set_flat_outputs(None, None)
+            env.set_flat_scalars(None, None, None)
+        self._started = False

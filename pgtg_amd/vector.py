@@ -569,6 +569,15 @@ class PGTGVecEnv:
         snap.save(self, src, None)
         snap.load(self, torch.arange(src.numel(), device=self.device), dst, observe=observe, check=check)
 
+    # -- PPO rollout buffer on the device (SB3's RolloutBuffer, pgtg/train.py:61-74) -------------------
+    def rollout(self, n_steps: int, gamma: float = 0.99, gae_lambda: float = 0.95, obs_dtype=None):
+        """A Rollout (pgtg_amd/rollout.py) of n_steps steps of this batch: the steps record themselves into
+        its rows, finish() is the HIP kernel k_gae.  obs_dtype: torch.int8 (default) or torch.float32.
+        Needs autoreset=True and a flattenable observation (ValueError otherwise).  While it records, the
+        Rollout owns this handle's flat bindings (set_flat_outputs / set_flat_scalars)."""
+        from .rollout import Rollout
+        return Rollout(self, n_steps, gamma, gae_lambda, obs_dtype)
+
     def _bound_tensors(self) -> list:
         """Every tensor a step launch writes: the outputs and whatever else is bound."""
         ts = [self.obs_map, self.position, self.velocity, self.reward, self.terminated, self.truncated, self.braking,
