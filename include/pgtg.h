@@ -18,6 +18,7 @@
  *                        wrapper the reference's caller puts around the vector env  pgtg/train.py:55
  *   pgtg_gae          <- (new, no reference function) RolloutBuffer.compute_returns_and_advantage of the
  *                        PPO the reference's caller trains                 pgtg/train.py:61-74
+ *   pgtg_flatten      <- (new, test-oriented) the FlattenObservation kernel alone, over the bound outputs
  *   pgtg_snapshot_*   <- copy.deepcopy(env) / env.clone() for single envs of the batch, on the device
  *                        environment.py:1283-1299, pgtg/evaluator.py:98-110
  *
@@ -285,6 +286,15 @@ int pgtg_set_flat_outputs(pgtg_handle* h, const int32_t* order, int32_t n_order,
  * vector env returns -- into these [N] device buffers (all three or none; needs the reward, terminated
  * and truncated outputs bound).  No reference function: it replaces per-step tensor arithmetic. */
 int pgtg_set_flat_scalars(pgtg_handle* h, float* reward_f32_dev, uint8_t* dones_dev, uint8_t* truncated_only_dev);
+/* k_flatten alone, over the bound outputs as they are now (tests: rows from chosen inputs, without a
+ * step, reset or observe launch rewriting the observation first).  mode: 0 the observation rows and
+ * the scalars of pgtg_set_flat_scalars, 1 the terminal rows of the envs whose terminated | truncated
+ * is set, 2 both -- the launch a step makes.  grid: 0 the grid a step uses, else that many workgroups,
+ * each taking ceil(N / grid) consecutive envs.  PGTG_E_INVALID with a message, nothing launched: a
+ * grid below ceil(N / 256) (the kernel lists at most 256 envs per workgroup) or above N, or a mode
+ * whose destination is not bound.  The same launch site as the step path's.  Asynchronous on the
+ * handle's stream. */
+int pgtg_flatten(pgtg_handle* h, int32_t mode, int32_t grid);
 /* Episode return and length per env (new; no reference function: it replaces SB3's VecMonitor wrapper of
  * pgtg/train.py:55, whose info["episode"] = {"r", "l"} feeds ep_rew_mean / ep_len_mean).  The handle
  * keeps per env a float32 return and an int32 length; with the two [N] buffers bound, every pgtg_step

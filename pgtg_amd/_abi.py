@@ -33,7 +33,7 @@ EXPORTED = [
     "pgtg_error_count", "pgtg_window", "pgtg_num_envs", "pgtg_launch_info", "pgtg_occupancy", "pgtg_step_kernel", "pgtg_last_error", "pgtg_enable_timing",
     "pgtg_timing_read", "pgtg_measure_hbm", "pgtg_state_size", "pgtg_dump_state", "pgtg_load_state",
     "pgtg_set_to_state", "pgtg_car_digest", "pgtg_get_queue_maps", "pgtg_get_queue_overflow", "pgtg_set_flat_outputs", "pgtg_set_flat_scalars",
-    "pgtg_set_episode_stats", "pgtg_episode_summary", "pgtg_gae",
+    "pgtg_set_episode_stats", "pgtg_episode_summary", "pgtg_gae", "pgtg_flatten",
     "pgtg_snapshot_create", "pgtg_snapshot_destroy", "pgtg_snapshot_bytes", "pgtg_snapshot_save", "pgtg_snapshot_load",
 ]
 
@@ -147,6 +147,7 @@ def lib():
         "pgtg_get_queue_overflow": ([vp, C.POINTER(u64)], C.c_int),
         "pgtg_set_flat_outputs": ([vp, C.POINTER(C.c_int32), i32, i32, vp, vp], C.c_int),
         "pgtg_set_flat_scalars": ([vp, vp, vp, vp], C.c_int),
+        "pgtg_flatten": ([vp, i32, i32], C.c_int),
         "pgtg_set_episode_stats": ([vp, vp, vp], C.c_int),
         "pgtg_episode_summary": ([vp, C.POINTER(PgtgEpisodeSummary), i32], C.c_int),
         "pgtg_gae": ([vp, C.POINTER(PgtgGae)], C.c_int),

@@ -4346,7 +4346,9 @@ template <typename T, bool ONE, int V>
 __global__ void __launch_bounds__(256, 6) k_flatten(FlatArgs a) {
   // obs byte offset of the row's first kFlatU x 64 values (channels in name order), built once
   __shared__ uint32_t offs[kFlatU * 64];
-  __shared__ uint32_t rows[512];  // t (observation row) or 256 + t (terminal row)
+  // t (observation row) or 256 + t (terminal row): K = 256 with every env finished fills it exactly
+  // (tests/test_gpu_flatten_kernel.py runs that case: 512 envs on 2 workgroups, mode 2)
+  __shared__ uint32_t rows[512];
   __shared__ uint32_t nrows;
   const int t = threadIdx.x;
   const uint32_t D = (uint32_t)a.D, w2 = (uint32_t)a.w2, cw2 = (uint32_t)a.cw2;
@@ -5344,7 +5346,8 @@ static int episode_zero(pgtg_handle* h, const uint8_t* mask) {
 
 // k_flatten over the bound observation (final: the terminal observations, finished envs' rows only)
 // mode: 0 the observation rows, 1 the terminal rows, 2 both (one launch after a step)
-static int launch_flatten(pgtg_handle* h, int mode) {
+// grid: 0 the production grid (the step path), else that many workgroups (pgtg_flatten, which checks it)
+static int launch_flatten(pgtg_handle* h, int mode, uint64_t grid) {
   FlatArgs a = h->flat;
   const PgtgOutputs& o = h->out;
   const bool final = mode == 1;
@@ -5382,7 +5385,7 @@ static int launch_flatten(pgtg_handle* h, int mode) {
   // rows per workgroup <= 256; one round of resident workgroups where the batch allows.  (The grid
   // hardly matters: 256 / 512 / 1 536 / 3 072 workgroups 150 / 138 / 139 / 134 us per step at 65 536
   // envs, profiles/r06/flat_grid_sweep.txt -- the kernel is bound chip-wide, not by waves in flight)
-  const uint64_t G = std::max<uint64_t>(std::min<uint64_t>(h->n, h->flat_wgs), (h->n + 255) / 256);
+  const uint64_t G = grid ? grid : std::max<uint64_t>(std::min<uint64_t>(h->n, h->flat_wgs), (h->n + 255) / 256);
   if (h->flat_dtype) {
     if (one) hipLaunchKernelGGL((k_flatten<int8_t, true, 1>), dim3((unsigned)G), dim3(256), 0, h->stream, a);
     else hipLaunchKernelGGL((k_flatten<int8_t, false, 1>), dim3((unsigned)G), dim3(256), 0, h->stream, a);
@@ -5436,7 +5439,7 @@ static int launch(pgtg_handle* h, const uint8_t* actions, const uint8_t* mask, i
   {
     const bool fl = h->flat_dst != nullptr, ff = h->final_flat_dst != nullptr && mode == MODE_STEP;
     if (fl || ff)  // (both row sets in one launch after a step)
-      if (int rc = launch_flatten(h, fl && ff ? 2 : (ff ? 1 : 0))) return rc;
+      if (int rc = launch_flatten(h, fl && ff ? 2 : (ff ? 1 : 0), 0)) return rc;
   }
   if (timed) {
     HIPCHK(h, hipEventRecord(h->evpool[h->ev_used + 1], h->stream));
@@ -6186,6 +6189,18 @@ int pgtg_set_flat_scalars(pgtg_handle* h, float* reward_f32_dev, uint8_t* dones_
   h->flat_dones = dones_dev;
   h->flat_tonly = truncated_only_dev;
   return PGTG_OK;
+}
+
+int pgtg_flatten(pgtg_handle* h, int32_t mode, int32_t grid) {
+  if (!h) return PGTG_E_INVALID;
+  if (mode < 0 || mode > 2) return fail(h, PGTG_E_INVALID, "pgtg_flatten: mode 0 observation rows, 1 terminal rows, 2 both");
+  if (mode != 1 && !h->flat_dst) return fail(h, PGTG_E_INVALID, "pgtg_flatten: no observation rows bound (pgtg_set_flat_outputs)");
+  if (mode != 0 && !h->final_flat_dst) return fail(h, PGTG_E_INVALID, "pgtg_flatten: no terminal rows bound (pgtg_set_flat_outputs)");
+  // (rows per workgroup K = ceil(n / grid) <= 256: k_flatten's row list holds 2 K entries; no empty tail of workgroups)
+  if (grid < 0 || (grid > 0 && ((uint64_t)grid < (h->n + 255) / 256 || (uint64_t)grid > h->n)))
+    return fail(h, PGTG_E_INVALID, "pgtg_flatten: grid must be 0 or between ceil(n / 256) and n workgroups");
+  HIPCHK(h, hipSetDevice(h->device));
+  return launch_flatten(h, mode, (uint64_t)grid);
 }
 
 int pgtg_set_episode_stats(pgtg_handle* h, float* ep_return_dev, int32_t* ep_length_dev) {

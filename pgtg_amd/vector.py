@@ -399,6 +399,14 @@ class PGTGVecEnv:
                                                ptr(flat), ptr(final_flat)), self._h)
         self._flat_refs = (flat, final_flat)  # (the handle writes into them: keep them alive)
 
+    def flatten_now(self, mode: int = 0, grid: int = 0) -> None:
+        """k_flatten alone over the bound tensors as they are now (include/pgtg.h pgtg_flatten; tests):
+        mode 0 the observation rows and the scalars, 1 the terminal rows of the finished envs, 2 both;
+        grid 0 the grid a step uses, else that many workgroups.  ValueError, nothing launched, for a grid
+        below ceil(num_envs / 256) or above num_envs and for a mode whose rows are not bound."""
+        self._bind_stream()
+        _check(self._lib.pgtg_flatten(self._h, int(mode), int(grid)), self._h)
+
     # -- episode statistics (SB3's VecMonitor for the batch, pgtg/train.py:55) -----------------------
     def enable_episode_stats(self, ep_return=None, ep_length=None):
         """Have every step also write each env's episode return (float32) and length (int32) so far
