@@ -113,10 +113,17 @@ def feature_channels(features: list[str]) -> list[tuple[str, int]]:
     return [(k, keys[k]) for k in order]
 
 
+INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
+SPEED_SQ_TOP = 2 * 30000 * 30000  # the step refuses |vx| or |vy| > 30 000 (PGTG_E_UNSUPPORTED)
+
+
 def _speed_sq_bounds(lo: float, hi: float, vmax: int = 1 << 15) -> tuple[int, int]:
     """Integer interval [smin, smax] of s = vx^2+vy^2 with lo <= sqrt(s) <= hi in fp64
     (np.linalg.norm of the int velocity, pgtg/environment.py:245-246).  sqrt is correctly rounded
-    and monotone, so the admissible s form an interval; smax < smin encodes 'never'."""
+    and monotone, so the admissible s form an interval; smax < smin encodes 'never'.  Both ends are
+    clamped to INT32_MAX, the int32 the device compares (include/pgtg.h PgtgRule): every speed the
+    step accepts has s <= SPEED_SQ_TOP < INT32_MAX, so an unbounded range keeps every such s and a
+    lower bound beyond them keeps none."""
     top = 2 * vmax * vmax
 
     def first_true(pred):  # smallest s in [0, top+1] with pred(s), pred monotone False->True
@@ -130,8 +137,19 @@ def _speed_sq_bounds(lo: float, hi: float, vmax: int = 1 << 15) -> tuple[int, in
         return b
 
     smin = first_true(lambda s: lo <= math.sqrt(s))
-    smax = first_true(lambda s: math.sqrt(s) > hi) - 1
-    return smin, smax
+    smax = first_true(lambda s: not math.sqrt(s) <= hi) - 1  # (a NaN bound admits nothing)
+    return min(smin, INT32_MAX), min(smax, INT32_MAX)
+
+
+def _threshold_i32(v) -> int:
+    """`count < v` on integer counts as an int32: the ceiling of v (a count is below 1.5 exactly when
+    it is below 2), clamped to the field (counts are far below 2^31, so a clamped bound decides alike)."""
+    v = float(v)
+    if math.isnan(v):
+        return INT32_MIN  # `count < nan` is False: the test never rejects
+    if math.isinf(v):
+        return INT32_MAX if v > 0 else INT32_MIN
+    return max(INT32_MIN, min(INT32_MAX, math.ceil(v)))
 
 
 @dataclass
@@ -161,10 +179,10 @@ def compile_rule(rule: dict[str, Any]) -> CompiledRule:
             d = AGENT_DIRECTIONS.index(m["agent"])
             for r, rname in enumerate(ROUTES):
                 if rname in m["traffic"]:
-                    w[d][r] += 1
+                    w[d][r] = min(w[d][r] + 1, 255)  # (a uint8 in both rule structs)
     smin, smax = _speed_sq_bounds(lo, hi)
-    return CompiledRule(rule["name"], mask, lo, hi, smin, smax, int(rule["min_traffic"]),
-                        int(rule["min_matching_traffic"]), w)
+    return CompiledRule(rule["name"], mask, lo, hi, smin, smax, _threshold_i32(rule["min_traffic"]),
+                        _threshold_i32(rule["min_matching_traffic"]), w)
 
 
 def _parse_position(pos, name: str, width: int, height: int):

@@ -14,7 +14,7 @@ TESTDATA = os.path.join(ROOT, "tests", "golden", "maps")
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from pgtg_amd.config import make_spec  # noqa: E402
+from pgtg_amd.config import add_rule, make_spec  # noqa: E402
 
 
 def load_traj(name: str) -> dict:
@@ -37,7 +37,12 @@ def spec_for(meta: dict):
     import warnings
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        return make_spec(mp, **kw)
+        spec = make_spec(mp, **kw)
+    if "rules" in meta:  # a case with its own traffic rules (tools/gen_golden.py RULE_CASES)
+        spec.rules = []
+        for r in meta["rules"]:
+            add_rule(spec, r)
+    return spec
 
 
 def digest(arr) -> int:
@@ -85,6 +90,8 @@ def replay_oracle(d: dict, n_envs: int | None = None, steps: int | None = None) 
                 bad.append(f"{tag} nsd {r['nsd']} vs {d['nsd'][t, i]}")
             if bool(r["braking"]) != bool(d["braking"][t, i]):
                 bad.append(f"{tag} braking")
+            if "triggered" in d and int(r["braking"]) != int(d["triggered"][t, i]):
+                bad.append(f"{tag} triggered rules {int(r['braking']):#04x} vs {int(d['triggered'][t, i]):#04x}")
             if digest(env.cars()) != int(d["cars_dig"][t, i]):
                 bad.append(f"{tag} cars")
             if r["terminated"]:
@@ -157,6 +164,8 @@ def replay_vec(d: dict, n_envs: int | None = None, steps: int | None = None) -> 
                 continue
             if bool(brk[i]) != bool(d["braking"][t, i]):
                 bad.append(f"{tag} braking {brk[i]} vs {d['braking'][t, i]}")
+            if "triggered" in d and int(brk[i]) != int(d["triggered"][t, i]):
+                bad.append(f"{tag} triggered rules {int(brk[i]):#04x} vs {int(d['triggered'][t, i]):#04x}")
             if rew[i] != d["reward"][t, i] or cost[i] != d["cost"][t, i]:
                 bad.append(f"{tag} reward {rew[i]} vs {d['reward'][t, i]} cost {cost[i]} vs {d['cost'][t, i]}")
             if term[i]:
@@ -186,3 +195,41 @@ def replay_vec(d: dict, n_envs: int | None = None, steps: int | None = None) -> 
                 return bad
     env.close()
     return bad
+
+
+def vec_vs_oracle(vec, spec_orc, n, steps, seed, rng, tag, envs=None, stats=None, orcs=None):
+    """Autoreset batch vs per-env oracles: reward, termination, observation and braking mask.  The
+    oracles are reset with seed + i, the batch is expected to have been.  `envs`: the env indices to
+    compare (default all n).  `stats` (dict): gets per-rule firing counts ("rule", 8 ints) and the
+    number of compared steps with two or more rules ("multi") added.  `orcs` (dict env -> OracleEnv):
+    oracles of an earlier call to carry on with (an empty dict is filled).  Returns the steps that braked."""
+    import torch
+    from oracle.oracle import OracleEnv
+    envs = list(range(n)) if envs is None else list(envs)
+    if not orcs:
+        orcs = {} if orcs is None else orcs
+        for i in envs:
+            orcs[i] = OracleEnv(spec_orc)
+            orcs[i].reset(seed + i)
+    fired = 0
+    for t in range(steps):
+        acts = rng.integers(0, 9, n).astype(np.uint8)
+        vec.step(torch.as_tensor(acts))
+        torch.cuda.synchronize()
+        m, rew = vec.obs_map.cpu().numpy(), vec.reward.cpu().numpy()
+        term, mask = vec.terminated.cpu().numpy(), vec.braking.cpu().numpy()
+        for i, o in orcs.items():
+            r = o.step(int(acts[i]))
+            assert rew[i] == r["reward"] and bool(term[i]) == r["terminated"], f"{tag} t{t} env{i}"
+            assert int(mask[i]) == int(r["braking"]), f"{tag} t{t} env{i} braking"
+            fired += int(mask[i] != 0)
+            if stats is not None:
+                b = int(r["braking"])
+                stats.setdefault("rule", [0] * 8)
+                for k in range(8):
+                    stats["rule"][k] += (b >> k) & 1
+                stats["multi"] = stats.get("multi", 0) + int(bin(b).count("1") >= 2)
+            if r["terminated"]:
+                r = o.reset(None)
+            assert np.array_equal(m[i], r["obs"]), f"{tag} t{t} env{i} obs"
+    return fired

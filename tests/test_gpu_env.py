@@ -6,7 +6,7 @@ import warnings
 import numpy as np
 import pytest
 
-import helpers  # noqa: F401  (sys.path)
+import helpers
 from oracle.oracle import OracleEnv
 from pgtg_amd import config as cfg
 
@@ -182,28 +182,7 @@ def test_triggered_mask_over_golden_braking_trajectory():
     vec.close()
 
 
-def _vec_vs_oracle(vec, spec_orc, n, steps, seed, rng, tag):
-    """Autoreset batch vs per-env oracles: reward, termination, observation and braking mask."""
-    import torch
-    orcs = [OracleEnv(spec_orc) for _ in range(n)]
-    for i, o in enumerate(orcs):
-        o.reset(seed + i)
-    fired = 0
-    for t in range(steps):
-        acts = rng.integers(0, 9, n).astype(np.uint8)
-        vec.step(torch.as_tensor(acts))
-        torch.cuda.synchronize()
-        m, rew = vec.obs_map.cpu().numpy(), vec.reward.cpu().numpy()
-        term, mask = vec.terminated.cpu().numpy(), vec.braking.cpu().numpy()
-        for i, o in enumerate(orcs):
-            r = o.step(int(acts[i]))
-            assert rew[i] == r["reward"] and bool(term[i]) == r["terminated"], f"{tag} t{t} env{i}"
-            assert int(mask[i]) == int(r["braking"]), f"{tag} t{t} env{i} braking"
-            fired += int(mask[i] != 0)
-            if r["terminated"]:
-                r = o.reset(None)
-            assert np.array_equal(m[i], r["obs"]), f"{tag} t{t} env{i} obs"
-    return fired
+_vec_vs_oracle = helpers.vec_vs_oracle
 
 
 def test_rules_added_to_a_ruleless_traffic_handle():

@@ -6,10 +6,15 @@ Vector semantics (what the batched product implements): env i is reset with seed
 then stepped with actions[t, i]; when it terminates it is reset unseeded (next spawn block), the
 gymnasium/SB3 auto-reset convention.  Recorded per (t, i): the step's returned observation
 (terminal one when it ended), reward, cost, terminated, position, velocity, next_subgoal_direction,
-a digest of the car list, and the post-reset observation of envs that were reset.
+a digest of the car list, the braking flag, the byte of triggered rules (bit r: rule r's name is in
+rule_engine.rule_triggers) and the post-reset observation of envs that were reset.
+
+A case of RULE_CASES carries its own traffic rules: after construction the env's default rules are
+removed and the case's are added through add_traffic_rule; the list is stored in the fixture's meta.
 
 Usage:  python tools/gen_golden.py [name ...]
 """
+import copy
 import json
 import os
 import sys
@@ -89,6 +94,113 @@ CONFIGS = {
 }
 
 
+
+
+# ---- cases with their own traffic rules ------------------------------------------------------------
+AGENTS4 = ["south_to_north", "west_to_east", "north_to_south", "east_to_west"]
+AGENTS6 = AGENTS4 + ["stationary", "near_goal"]
+SQRT2, SQRT5 = 2 ** 0.5, 5 ** 0.5
+
+
+def rule(name, tile, vr, mt, mm, maneuvers):
+    return {"name": name, "tile_type": tile, "velocity_range": list(vr), "min_traffic": mt,
+            "min_matching_traffic": mm, "maneuvers": maneuvers}
+
+
+def every(agents, routes):
+    return [{"agent": a, "traffic": list(routes)} for a in agents]
+
+
+EW = ["west_to_east", "east_to_west"]
+NS = ["north_to_south", "south_to_north"]
+FAST = [1.5, 10]  # fires from speed 2 on only, so the agent can creep through the tile at speed 1 or sqrt(2)
+# (a rule that fires at the speeds one acceleration gives pins the agent for as long as the cars stay)
+RULE_SETS = {
+    "default": None,  # the constructor's two rules
+    # thresholds above 1 on straight and corner tiles
+    "thr_a": [rule("two_in_0101", "0101", FAST, 2, 2, every(AGENTS6, ROUTES)),
+              rule("three_in_0101", "0101", FAST, 3, 2, every(AGENTS6, ROUTES)),
+              rule("two_in_1010", "1010", FAST, 2, 1, every(AGENTS6, ROUTES)),
+              rule("three_in_1010", "1010", FAST, 3, 3, every(AGENTS6, ROUTES))] +
+             [rule(f"two_in_{t}", t, FAST, 2, 2, every(AGENTS6, ROUTES)) for t in ("1100", "0110", "0011", "1001")],
+    # ... and on T-junctions and the crossing, some matching only part of the routes
+    "thr_b": [rule("two_in_1110", "1110", FAST, 2, 2, every(AGENTS6, ROUTES)),
+              rule("three_ns_in_1010", "1010", FAST, 3, 3, every(AGENTS6, NS)),
+              rule("two_ew_in_0101", "0101", FAST, 2, 2, every(AGENTS6, EW)),
+              rule("three_of_two_ew_in_0101", "0101", FAST, 3, 2, every(AGENTS6, EW)),
+              rule("two_in_1101", "1101", FAST, 2, 2, every(AGENTS6, ROUTES)),
+              rule("three_in_0111", "0111", FAST, 3, 3, every(AGENTS6, ROUTES)),
+              rule("two_in_1011", "1011", FAST, 2, 2, every(AGENTS6, ROUTES)),
+              rule("three_in_1111", "1111", FAST, 3, 3, every(AGENTS6, ROUTES))],
+    # one route named by two (three) maneuvers of one agent direction: a single such car counts twice
+    "dup": [rule("twice", "1111", FAST, 1, 2, every(["west_to_east"], NS[:1]) * 2),
+            rule("once", "1111", FAST, 1, 2, every(["west_to_east"], NS[:1])),
+            rule("thrice", "1111", FAST, 1, 3, every(["west_to_east"], NS[1:]) * 3),
+            rule("twice_in_one_list", "1111", FAST, 1, 2, every(["west_to_east"], NS[1:] * 2))],
+    # agent directions 4 and 5: no goal square in compass reach, at speed 0 and above
+    "still": [rule("near_goal_moving", "1111", [1, 10], 1, 1, every(["near_goal"], ROUTES)),
+              rule("stationary_0", "1111", [0, 0], 1, 1, every(["stationary"], ROUTES)),
+              rule("stationary_two", "1111", [0, 0.05], 2, 2, every(["stationary"], ROUTES[:10])),
+              rule("near_goal_slow", "1111", [0.1, SQRT2], 2, 1, every(["near_goal"], ROUTES[10:])),
+              rule("stationary_never", "1111", [0.1, 3], 0, 1, every(["stationary"], ROUTES)),
+              rule("near_goal_never", "1111", [0, 0], 0, 1, every(["near_goal"], ROUTES))],
+    # all eight slots, speed bounds at equality and at irrational endpoints
+    "eight": [rule("v_0_0", "1111", [0, 0], 1, 1, every(["stationary"], ROUTES)),
+              rule("v_0_1", "1111", [0, 1], 1, 1, every(["stationary", "near_goal"], ROUTES)),
+              rule("v_1_sqrt2", "1111", [1, SQRT2], 1, 1, every(["near_goal"], ROUTES)),
+              rule("v_sqrt2_sqrt2", "1111", [SQRT2, SQRT2], 1, 1, every(["near_goal"], ROUTES)),
+              rule("v_1.5_sqrt5", "1111", [1.5, SQRT5], 1, 1, every(["west_to_east"], ROUTES)),
+              rule("v_2_3", "1111", [2, 3], 2, 2, every(["west_to_east"], ROUTES)),
+              rule("v_1.5_inf", "1111", [1.5, float("inf")], 3, 1, every(["west_to_east", "near_goal"], ROUTES)),
+              rule("v_2_1e9", "1111", [2, 1e9], 4, 4, every(AGENTS6, ROUTES))],
+    # names the engine never matches, beside two rules that fire
+    "malformed": [rule("tile_5_chars", "11110", [0, 10], 0, 0, every(AGENTS6, ROUTES)),
+                  rule("tile_letters", "1x11", [0, 10], 0, 0, every(AGENTS6, ROUTES)),
+                  rule("tile_int", 1111, [0, 10], 0, 0, every(AGENTS6, ROUTES)),
+                  rule("unknown_agent", "1111", [0, 10], 1, 1, every(["sideways", "north"], ROUTES)),
+                  rule("unknown_routes", "1111", [0, 10], 1, 1, every(AGENTS6, ["up_to_down", "all"])),
+                  rule("any_car", "1111", FAST, 1, 1, every(AGENTS6, ROUTES)),
+                  rule("no_car_needed", "1111", FAST, 0, 0, [])],
+    # the fixed maps' tile types
+    "directions": [rule(f"{n}in_{t}", t, [2.5, 10], mt, mt, every(AGENTS6, ROUTES))
+                   for t in ("1001", "1010") for n, mt in (("", 1), ("two_", 2))],
+    "deadends": [rule(f"{n}in_{t}", t, [2.5, 10], mt, mt, every(AGENTS6, ROUTES))
+                 for t in ("1101", "0101", "0010") for n, mt in (("", 1), ("two_", 2))],
+    "straight": [rule("any", "0101", FAST, 1, 1, every(AGENTS6, ROUTES)),
+                 rule("oncoming_twice", "0101", FAST, 2, 2, every(["west_to_east"], ["east_to_west"])),
+                 rule("same_way_three", "0101", [1.5, 3], 3, 3, every(["west_to_east"], ["west_to_east"]))],
+}
+# name: (kwargs, map_path, n_envs, steps, action_mode, rule set, seed_base, action seed,
+#        rules that must have fired (None: all), rules that must never have fired)
+RULE_CASES = {
+    "rules_default_s5": (dict(random_map_width=5, random_map_height=5, traffic_density=0.5,
+                              random_map_start_position="random", random_map_goal_position="random"), None, 8, 40,
+                         "cautious", "default", 400, 4, None, ()),
+    "rules_thr_a_s4": (dict(random_map_width=4, random_map_height=4, traffic_density=1.0,
+                            ignore_traffic_collisions=True, random_map_start_position="random",
+                            random_map_goal_position="random"), None, 8, 40, "uniform", "thr_a", 0, 12345, None, ()),
+    "rules_thr_b_s5": (dict(random_map_width=5, random_map_height=5, traffic_density=0.5,
+                            ignore_traffic_collisions=True, random_map_start_position="random",
+                            random_map_goal_position="random"), None, 8, 40, "uniform", "thr_b", 0, 12345, None, ()),
+    "rules_dup_crossing": (dict(traffic_density=0.5, ignore_traffic_collisions=True), "1x1_crossing_map", 8, 40,
+                           "cautious", "dup", 0, 12345, None, ()),
+    "rules_still_crossing": (dict(traffic_density=0.5, ignore_traffic_collisions=True), "1x1_crossing_map", 6, 40,
+                             "cautious", "still", 0, 12345, (0, 1, 2, 3), (4, 5)),
+    "rules_eight_crossing": (dict(traffic_density=0.5, ignore_traffic_collisions=True), "1x1_crossing_map", 6, 40,
+                             "cautious", "eight", 0, 12345, None, ()),
+    "rules_malformed_crossing": (dict(traffic_density=0.5, ignore_traffic_collisions=True), "1x1_crossing_map", 4,
+                                 30, "cautious", "malformed", 0, 12345, (5, 6), (0, 1, 2, 3, 4)),
+    "rules_fixed_directions": (dict(traffic_density=0.7, ignore_traffic_collisions=True),
+                               "map_with_all_directions", 6, 60, "uniform", "directions", 200, 2, None, ()),
+    "rules_fixed_deadends": (dict(traffic_density=0.7, ignore_traffic_collisions=True), "map_with_all_deadends",
+                             6, 60, "uniform", "deadends", 100, 1, None, ()),
+    "rules_fixed_4x1": (dict(traffic_density=0.8, ignore_traffic_collisions=True), "4x1_map.json", 6, 40,
+                        "cautious", "straight", 0, 12345, None, ()),
+}
+# pairs (a, b): some step must have fired rule a without rule b
+FIRED_WITHOUT = {"rules_dup_crossing": [[0, 1], [2, 3]]}
+
+
 def actions_for(mode, T, N, seed):
     rng = np.random.default_rng(seed)
     if mode == "uniform":
@@ -130,15 +242,28 @@ def plan_rows(env):
                 goal=[int(mp.goal[0]), int(mp.goal[1]), dirs.index(mp.goal[2])])
 
 
-def run(name):
-    kwargs, map_file, N, T, mode = CONFIGS[name]
+def run(name, write=True, seeds=None):
+    rules, seed_base, act_seed = None, 0, 12345
+    if name in RULE_CASES:
+        kwargs, map_file, N, T, mode, rule_set, seed_base, act_seed, expect, never = RULE_CASES[name]
+        if seeds:  # (a seed search, write=False)
+            seed_base, act_seed = seeds
+        rules = RULE_SETS[rule_set]
+    else:
+        kwargs, map_file, N, T, mode = CONFIGS[name]
     map_path = os.path.join(TESTDATA, map_file) if map_file else None
-    seed_base = 0
-    acts = actions_for(mode, T, N, 12345)
+    acts = actions_for(mode, T, N, act_seed)
     cwd = os.getcwd()
     os.chdir(REPO)
     envs = [env_mod.PGTGEnv(map_path, **kwargs) for _ in range(N)]
     os.chdir(cwd)
+    if rules is not None:
+        for e in envs:
+            for r in list(e.rule_engine.rules):
+                e.remove_traffic_rule(r.name)
+            for r in rules:
+                e.add_traffic_rule(copy.deepcopy(r))
+    rule_names = [r.name for r in envs[0].rule_engine.rules]
     first = [e.reset(seed=seed_base + i)[0] for i, e in enumerate(envs)]
     keys = list(first[0]["map"].keys())
     W = np.asarray(first[0]["map"][keys[0]]).shape[0]
@@ -154,6 +279,7 @@ def run(name):
     term = np.zeros((T, N), np.uint8)
     nsd = np.zeros((T, N), np.int32)
     brake = np.zeros((T, N), np.uint8)
+    trig = np.zeros((T, N), np.uint8)
     cars_dig = np.zeros((T, N), np.uint32)
     ncars = np.zeros((T, N), np.int32)
     reset_obs, reset_idx, reset_pos, reset_nsd, reset_dig = [], [], [], [], []
@@ -171,6 +297,7 @@ def run(name):
             term[t, i] = bool(te)
             nsd[t, i] = o.get("next_subgoal_direction", -1)
             brake[t, i] = bool(e.braking_applied)
+            trig[t, i] = sum(1 << k for k, n in enumerate(rule_names) if n in e.rule_engine.rule_triggers)
             cr = car_rows(e)
             cars_dig[t, i] = digest(cr)
             ncars[t, i] = len(cr)
@@ -186,7 +313,15 @@ def run(name):
         cars_final.append(car_rows(e))
     meta = dict(name=name, kwargs=kwargs, map_file=map_file, N=N, T=T, seed_base=seed_base, keys=keys,
                 action_mode=mode, plans=plans)
+    if name in RULE_CASES:
+        meta.update(action_seed=act_seed, rule_names=rule_names, never_fired=list(never),
+                    expect_fired=list(range(len(rule_names))) if expect is None else list(expect),
+                    fired_without=FIRED_WITHOUT.get(name, []))
+        if rules is not None:
+            meta["rules"] = rules
     R = len(reset_idx)
+    if not write:
+        return trig
     np.savez_compressed(
         os.path.join(OUT, f"traj_{name}.npz"),
         meta=np.frombuffer(json.dumps(meta).encode(), np.uint8), actions=acts,
@@ -200,7 +335,7 @@ def run(name):
         reset_nsd=np.array(reset_nsd, np.int32).reshape(R),
         reset_cars_dig=np.array(reset_dig, np.uint32).reshape(R),
         cars_final=np.concatenate(cars_final) if cars_final else np.zeros((0, 7), np.int32),
-        cars_final_n=np.array([len(c) for c in cars_final], np.int32),
+        cars_final_n=np.array([len(c) for c in cars_final], np.int32), triggered=trig,
     )
     return R, int(term.sum())
 
@@ -266,7 +401,7 @@ def rng_vectors():
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    names = sys.argv[1:] or list(CONFIGS)
+    names = sys.argv[1:] or list(CONFIGS) + list(RULE_CASES)
     if not sys.argv[1:]:
         rng_vectors()
         reproducibility_fixture()
