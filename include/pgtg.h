@@ -18,6 +18,8 @@
  *                        wrapper the reference's caller puts around the vector env  pgtg/train.py:55
  *   pgtg_gae          <- (new, no reference function) RolloutBuffer.compute_returns_and_advantage of the
  *                        PPO the reference's caller trains                 pgtg/train.py:61-74
+ *   pgtg_policy / pgtg_policy_pack <- (new, no reference function) the acting forward pass of the
+ *                        MlpPolicy that PPO collects with                  pgtg/train.py:61-74
  *   pgtg_flatten      <- (new, test-oriented) the FlattenObservation kernel alone, over the bound outputs
  *   pgtg_snapshot_*   <- copy.deepcopy(env) / env.clone() for single envs of the batch, on the device
  *                        environment.py:1283-1299, pgtg/evaluator.py:98-110
@@ -342,6 +344,45 @@ typedef struct {
   float* advantages; float* returns;   /* [T][N] */
 } PgtgGae;
 int pgtg_gae(pgtg_handle* h, const PgtgGae* a);
+/* The acting forward pass of SB3's MlpPolicy over int8 flat rows (new; no reference function: it replaces
+ * ActorCriticPolicy.forward / predict_values of the PPO("MlpPolicy") of pgtg/train.py:61-74 inside
+ * collect_rollouts).  Separate pi / vf towers, 64-64, tanh, 9 actions; float32 throughout.  Per env e,
+ * x = the obs_dim signed bytes of its row (row e starts at byte e * obs_dim of obs; any base alignment):
+ *   h1p = tanh(W1p x + b1p)   h2p = tanh(W2p h1p + b2p)   logits = Wa h2p + ba   (9)
+ *   h1v = tanh(W1v x + b1v)   h2v = tanh(W2v h1v + b2v)   value  = Wv h2v + bv
+ *   log_prob = logits[a] - (max + log(sum exp(logits - max)))
+ * mode PGTG_POLICY_SAMPLE: p = exp(logits - max) / sum in float32, c_a its running sum in action order,
+ *   a = the least a with u < c_a, 8 if there is none; u = uniforms[e] if uniforms is given, otherwise the
+ *   counter-based hash of (seed, counter, env_offset + e) (pgtg_amd.policy.policy_uniform: 24 bits in [0, 1)).
+ * mode PGTG_POLICY_ARGMAX: a = the least index among the maxima (predict(deterministic=True)).
+ * mode PGTG_POLICY_VALUE_ONLY: the vf tower alone; only values is written (and is required).
+ * actions, values, log_probs: [n] each, NULL = not written.  No load touches a byte outside
+ * [obs, obs + n * obs_dim).  One launch of k_policy, asynchronous on the handle's stream; the handle gives
+ * the device, the stream and the error string only (n and obs_dim need not be its own).  obs_dim == 0 or
+ * beyond PGTG_POLICY_MAX_OBS_DIM, obs or packed NULL (packed: 16-byte aligned), an unknown mode or
+ * n * obs_dim overflowing: PGTG_E_INVALID with a message, nothing is launched.  n == 0 is a no-op.
+ *
+ * packed is the kernel's own weight layout, written by pgtg_policy_pack (one launch of k_policy_pack on the
+ * handle's stream, no host copy; once per PPO update) from twelve device pointers in SB3's nn.Linear
+ * layouts, float32, contiguous: w1* [64][obs_dim], w2* [64][64], wa [9][64], wv [1][64] and their biases.
+ * pgtg_policy_packed_bytes gives the buffer's size for an obs_dim; pgtg_policy_chunk the observation
+ * bytes of a row the kernel stages at a time (tests place obs_dim around it). */
+#define PGTG_POLICY_SAMPLE 0
+#define PGTG_POLICY_ARGMAX 1
+#define PGTG_POLICY_VALUE_ONLY 2
+#define PGTG_POLICY_MAX_OBS_DIM 1048576
+typedef struct {
+  const float *w1p, *b1p, *w2p, *b2p, *wa, *ba;   /* mlp_extractor.policy_net.{0,2}, action_net */
+  const float *w1v, *b1v, *w2v, *b2v, *wv, *bv;   /* mlp_extractor.value_net.{0,2}, value_net */
+  uint64_t obs_dim;
+} PgtgPolicyWeights;
+typedef struct { uint64_t n, obs_dim; const int8_t* obs; const void* packed;
+                 int32_t mode; uint64_t seed, counter, env_offset;
+                 const float* uniforms; uint8_t* actions; float* values; float* log_probs; } PgtgPolicy;
+int pgtg_policy_packed_bytes(uint64_t obs_dim, uint64_t* bytes);
+int pgtg_policy_pack(pgtg_handle* h, const PgtgPolicyWeights* raw, void* packed);
+int pgtg_policy(pgtg_handle* h, const PgtgPolicy* a);
+int pgtg_policy_chunk(void);
 /* Re-emit the observation of every env into the bound outputs (after set_agent/add_car). */
 int pgtg_observe(pgtg_handle* h);
 /* Per-env uint64 digest of the car list into out_dev[N] (device; parity tests: the car term of

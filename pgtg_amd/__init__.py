@@ -18,6 +18,9 @@ def __getattr__(name):
     if name == "Rollout":
         from .rollout import Rollout
         return Rollout
+    if name in ("DevicePolicy", "MlpPolicyReference"):  # (SB3's MlpPolicy: the kernel k_policy and its yardstick)
+        from . import policy
+        return getattr(policy, name)
     if name == "PGTGEnv":
         from .env import PGTGEnv
         return PGTGEnv

@@ -34,6 +34,7 @@ EXPORTED = [
     "pgtg_timing_read", "pgtg_measure_hbm", "pgtg_state_size", "pgtg_dump_state", "pgtg_load_state",
     "pgtg_set_to_state", "pgtg_car_digest", "pgtg_get_queue_maps", "pgtg_get_queue_overflow", "pgtg_set_flat_outputs", "pgtg_set_flat_scalars",
     "pgtg_set_episode_stats", "pgtg_episode_summary", "pgtg_gae", "pgtg_flatten",
+    "pgtg_policy", "pgtg_policy_pack", "pgtg_policy_packed_bytes", "pgtg_policy_chunk",
     "pgtg_snapshot_create", "pgtg_snapshot_destroy", "pgtg_snapshot_bytes", "pgtg_snapshot_save", "pgtg_snapshot_load",
 ]
 
@@ -101,6 +102,21 @@ class PgtgGae(C.Structure):
                                   "advantages", "returns")]
 
 
+PGTG_POLICY_SAMPLE, PGTG_POLICY_ARGMAX, PGTG_POLICY_VALUE_ONLY = 0, 1, 2
+PGTG_POLICY_MAX_OBS_DIM = 1048576
+POLICY_WEIGHT_FIELDS = ("w1p", "b1p", "w2p", "b2p", "wa", "ba", "w1v", "b1v", "w2v", "b2v", "wv", "bv")
+
+
+class PgtgPolicyWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in POLICY_WEIGHT_FIELDS] + [("obs_dim", C.c_uint64)]
+
+
+class PgtgPolicy(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("obs_dim", C.c_uint64), ("obs", C.c_void_p), ("packed", C.c_void_p),
+                ("mode", C.c_int32), ("seed", C.c_uint64), ("counter", C.c_uint64), ("env_offset", C.c_uint64),
+                ("uniforms", C.c_void_p), ("actions", C.c_void_p), ("values", C.c_void_p), ("log_probs", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -151,6 +167,10 @@ def lib():
         "pgtg_set_episode_stats": ([vp, vp, vp], C.c_int),
         "pgtg_episode_summary": ([vp, C.POINTER(PgtgEpisodeSummary), i32], C.c_int),
         "pgtg_gae": ([vp, C.POINTER(PgtgGae)], C.c_int),
+        "pgtg_policy": ([vp, C.POINTER(PgtgPolicy)], C.c_int),
+        "pgtg_policy_pack": ([vp, C.POINTER(PgtgPolicyWeights), vp], C.c_int),
+        "pgtg_policy_packed_bytes": ([u64, C.POINTER(u64)], C.c_int),
+        "pgtg_policy_chunk": ([], C.c_int),
         "pgtg_snapshot_create": ([vp, u64, C.POINTER(vp)], C.c_int),
         "pgtg_snapshot_destroy": ([vp], C.c_int),
         "pgtg_snapshot_bytes": ([vp, C.POINTER(u64), C.POINTER(u64)], C.c_int),

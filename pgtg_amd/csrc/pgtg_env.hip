@@ -28,6 +28,7 @@
 #include "pgtg_device.h"
 #include "pgtg_episode.h"
 #include "pgtg_rollout.h"
+#include "pgtg_policy.h"
 #include "pgtg_snapshot.h"
 
 namespace pgtg {
@@ -6290,6 +6291,72 @@ int pgtg_gae(pgtg_handle* h, const PgtgGae* a) {
   HIPCHK(h, hipSetDevice(h->device));
   if (g.tonly) hipLaunchKernelGGL(k_gae<true>, dim3((unsigned)grid), dim3(kGaeBlock), 0, h->stream, g);
   else hipLaunchKernelGGL(k_gae<false>, dim3((unsigned)grid), dim3(kGaeBlock), 0, h->stream, g);
+  HIPCHK(h, hipGetLastError());
+  return PGTG_OK;
+}
+
+// The MlpPolicy forward pass (pgtg_policy.h): the handle gives the device, the stream and the error string
+int pgtg_policy_chunk(void) { return kPolChunk; }
+
+int pgtg_policy_packed_bytes(uint64_t obs_dim, uint64_t* bytes) {
+  if (!bytes || obs_dim == 0 || obs_dim > kPolMaxObsDim) return PGTG_E_INVALID;
+  *bytes = policy_layout(obs_dim).total * sizeof(float);
+  return PGTG_OK;
+}
+
+int pgtg_policy_pack(pgtg_handle* h, const PgtgPolicyWeights* raw, void* packed) {
+  if (!h) return PGTG_E_INVALID;
+  if (!raw || !packed) return fail(h, PGTG_E_INVALID, "pgtg_policy_pack: no weights or no packed buffer");
+  if (raw->obs_dim == 0 || raw->obs_dim > kPolMaxObsDim)
+    return fail(h, PGTG_E_INVALID, "pgtg_policy_pack: obs_dim outside [1, PGTG_POLICY_MAX_OBS_DIM]");
+  if (!raw->w1p || !raw->b1p || !raw->w2p || !raw->b2p || !raw->wa || !raw->ba || !raw->w1v || !raw->b1v ||
+      !raw->w2v || !raw->b2v || !raw->wv || !raw->bv)
+    return fail(h, PGTG_E_INVALID, "pgtg_policy_pack: all twelve weight pointers are required");
+  if ((uintptr_t)packed & 15u) return fail(h, PGTG_E_INVALID, "pgtg_policy_pack: packed must be 16-byte aligned");
+  PolicyPackArgs p = {raw->w1p, raw->b1p, raw->w2p, raw->b2p, raw->wa, raw->ba, raw->w1v, raw->b1v,
+                      raw->w2v, raw->b2v, raw->wv,  raw->bv,  (float*)packed, raw->obs_dim};
+  const uint64_t total = policy_layout(raw->obs_dim).total;
+  const uint64_t grid = std::min<uint64_t>((total + 255) / 256, 4096);
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_policy_pack, dim3((unsigned)grid), dim3(256), 0, h->stream, p);
+  HIPCHK(h, hipGetLastError());
+  return PGTG_OK;
+}
+
+int pgtg_policy(pgtg_handle* h, const PgtgPolicy* a) {
+  if (!h) return PGTG_E_INVALID;
+  if (!a) return fail(h, PGTG_E_INVALID, "pgtg_policy: no arguments");
+  if (a->obs_dim == 0) return fail(h, PGTG_E_INVALID, "pgtg_policy: obs_dim must be at least 1");
+  if (a->obs_dim > kPolMaxObsDim)
+    return fail(h, PGTG_E_INVALID, "pgtg_policy: obs_dim beyond PGTG_POLICY_MAX_OBS_DIM, the largest the pack supports");
+  if (!a->obs || !a->packed) return fail(h, PGTG_E_INVALID, "pgtg_policy: obs and packed are required");
+  if ((uintptr_t)a->packed & 15u) return fail(h, PGTG_E_INVALID, "pgtg_policy: packed must be 16-byte aligned");
+  if (a->mode != PGTG_POLICY_SAMPLE && a->mode != PGTG_POLICY_ARGMAX && a->mode != PGTG_POLICY_VALUE_ONLY)
+    return fail(h, PGTG_E_INVALID, "pgtg_policy: mode 0 sample, 1 argmax, 2 value only");
+  if (a->mode == PGTG_POLICY_VALUE_ONLY && !a->values)
+    return fail(h, PGTG_E_INVALID, "pgtg_policy: value-only mode needs the values output");
+  if (a->n > (UINT64_MAX >> 1) / a->obs_dim || (uintptr_t)a->obs > UINTPTR_MAX - a->n * a->obs_dim)
+    return fail(h, PGTG_E_INVALID, "pgtg_policy: n * obs_dim overflows");
+  if (a->n == 0) return PGTG_OK;
+  const uint64_t grid = (a->n + kPolRows - 1) / kPolRows;
+  if (grid > 0x7fffffffull) return fail(h, PGTG_E_UNSUPPORTED, "pgtg_policy: the batch is too large for one launch");
+  PolicyArgs p;
+  p.obs = a->obs;
+  p.packed = (const float*)a->packed;
+  p.uniforms = a->uniforms;
+  p.actions = a->actions;
+  p.values = a->values;
+  p.log_probs = a->log_probs;
+  p.n = a->n;
+  p.obs_dim = a->obs_dim;
+  p.seed = a->seed;
+  p.counter = a->counter;
+  p.env_offset = a->env_offset;
+  HIPCHK(h, hipSetDevice(h->device));
+  const dim3 g((unsigned)grid), b(kPolThreads);
+  if (a->mode == PGTG_POLICY_SAMPLE) hipLaunchKernelGGL(k_policy<POLICY_SAMPLE>, g, b, 0, h->stream, p);
+  else if (a->mode == PGTG_POLICY_ARGMAX) hipLaunchKernelGGL(k_policy<POLICY_ARGMAX>, g, b, 0, h->stream, p);
+  else hipLaunchKernelGGL(k_policy<POLICY_VALUE_ONLY>, g, b, 0, h->stream, p);
   HIPCHK(h, hipGetLastError());
   return PGTG_OK;
 }

@@ -1,0 +1,242 @@
+"""SB3's MlpPolicy for acting, on the device: the policy of the PPO of pgtg/train.py:61-74.
+
+`PPO("MlpPolicy", env)` builds an `ActorCriticPolicy` with two separate 64-64 tanh towers, a 9-way
+categorical head and a scalar value head.  `DevicePolicy` runs its forward pass for acting as one launch
+of the HIP kernel k_policy (include/pgtg.h pgtg_policy): it reads the int8 flat rows where k_flatten left
+them and writes the action, the value and the log-probability of every env into the rows it is given --
+`Rollout.collect(policy)` is a whole rollout without a torch kernel or a host synchronisation.  The PPO
+update stays in torch: `MlpPolicyReference` is the module a trainer optimises (SB3's parameter names and
+initialisation, so a real `policy.state_dict()` loads into it), and `DevicePolicy.load_state_dict` hands
+the updated weights to the kernel by a device-side repack (k_policy_pack).
+
+    policy = DevicePolicy(env)
+    policy.load_state_dict(module.state_dict())         # after every PPO update
+    ro.collect(policy)
+
+`policy_reference` restates the whole function in numpy at a chosen precision and `policy_uniform` the
+kernel's counter-based uniform draw (SB3 is not a dependency; the restatements are the tests' yardstick,
+as gae_reference is).
+"""
+from __future__ import annotations
+
+import collections
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _abi
+
+HIDDEN = 64
+N_ACTIONS = 9
+K_CHUNK = 256  # observation bytes of a row the kernel stages at a time (pgtg_policy_chunk())
+SAMPLE, ARGMAX, VALUE_ONLY = _abi.PGTG_POLICY_SAMPLE, _abi.PGTG_POLICY_ARGMAX, _abi.PGTG_POLICY_VALUE_ONLY
+
+# ABI field -> (state-dict key, shape with D for obs_dim)
+WEIGHT_KEYS = {
+    "w1p": ("mlp_extractor.policy_net.0.weight", (HIDDEN, "D")), "b1p": ("mlp_extractor.policy_net.0.bias", (HIDDEN,)),
+    "w2p": ("mlp_extractor.policy_net.2.weight", (HIDDEN, HIDDEN)), "b2p": ("mlp_extractor.policy_net.2.bias", (HIDDEN,)),
+    "wa": ("action_net.weight", (N_ACTIONS, HIDDEN)), "ba": ("action_net.bias", (N_ACTIONS,)),
+    "w1v": ("mlp_extractor.value_net.0.weight", (HIDDEN, "D")), "b1v": ("mlp_extractor.value_net.0.bias", (HIDDEN,)),
+    "w2v": ("mlp_extractor.value_net.2.weight", (HIDDEN, HIDDEN)), "b2v": ("mlp_extractor.value_net.2.bias", (HIDDEN,)),
+    "wv": ("value_net.weight", (1, HIDDEN)), "bv": ("value_net.bias", (1,)),
+}
+
+PolicyOutput = collections.namedtuple("PolicyOutput", "actions values log_probs logits")
+
+
+def weight_shapes(obs_dim: int) -> dict:
+    """{state-dict key: shape} of SB3's MlpPolicy for a flat observation of obs_dim values."""
+    return {key: tuple(obs_dim if s == "D" else s for s in shape) for key, shape in WEIGHT_KEYS.values()}
+
+
+def policy_uniform(seed: int, counter: int, env):
+    """The kernel's own uniform draw: float32 in [0, 1), a multiple of 2^-24, from splitmix64 of
+    (seed, draw counter, global env index) -- no state anywhere.  env: an int or an array of ints."""
+    M = (1 << 64) - 1
+    with np.errstate(over="ignore"):
+        e = np.asarray(env, dtype=np.uint64)
+        z = np.uint64(seed & M) ^ np.uint64((counter * 0x9E3779B97F4A7C15) & M) ^ (e * np.uint64(0xD1B54A32D192ED03))
+        z = z ^ np.uint64(0x706F6C6963795F75)
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return ((z >> np.uint64(40)).astype(np.float64) * 2.0 ** -24).astype(np.float32)
+
+
+def inverse_cdf(logits, u, dtype=np.float64):
+    """The kernel's sampling rule at precision dtype: p = exp(logits - max) / sum, c_a its running sum in
+    action order, the action is the least a with u < c_a, and 8 where rounding leaves c_8 <= u.
+    logits [N, 9], u [N]; returns (actions uint8 [N], c [N, 9])."""
+    lg = np.asarray(logits, dtype=dtype)
+    ex = np.exp(lg - lg.max(axis=1, keepdims=True))
+    p = ex / ex.sum(axis=1, keepdims=True, dtype=dtype)
+    c = np.zeros_like(p)
+    run = np.zeros(len(p), dtype=dtype)
+    for a in range(p.shape[1]):  # (a running sum in action order, at dtype)
+        run = (run + p[:, a]).astype(dtype)
+        c[:, a] = run
+    below = np.asarray(u, dtype=dtype)[:, None] < c
+    act = np.where(below.any(axis=1), below.argmax(axis=1), p.shape[1] - 1)
+    return act.astype(np.uint8), c
+
+
+def policy_reference(state_dict, obs_int8, uniforms=None, mode=SAMPLE, dtype=np.float64, *, seed=0, counter=0,
+                     env_offset=0) -> PolicyOutput:
+    """What k_policy computes, in numpy at precision dtype: obs_int8 [N, D] signed bytes, uniforms [N]
+    (SAMPLE; None draws policy_uniform(seed, counter, env_offset + e)).  Returns PolicyOutput(actions uint8,
+    values, log_probs, logits [N, 9]); VALUE_ONLY gives None for everything but values."""
+    if mode not in (SAMPLE, ARGMAX, VALUE_ONLY):
+        raise ValueError("mode: SAMPLE, ARGMAX or VALUE_ONLY")
+    x = np.asarray(obs_int8)
+    if x.dtype != np.int8 or x.ndim != 2:
+        raise ValueError("obs_int8: an int8 [N, D] array")
+    w = {f: np.asarray(_host(state_dict[key]), dtype=dtype) for f, (key, _) in WEIGHT_KEYS.items()}
+    x = x.astype(dtype)
+    tower = lambda w1, b1, w2, b2: np.tanh(np.tanh(x @ w[w1].T + w[b1]) @ w[w2].T + w[b2])  # noqa: E731
+    values = (tower("w1v", "b1v", "w2v", "b2v") @ w["wv"].T + w["bv"])[:, 0]
+    if mode == VALUE_ONLY:
+        return PolicyOutput(None, values, None, None)
+    logits = tower("w1p", "b1p", "w2p", "b2p") @ w["wa"].T + w["ba"]
+    if mode == ARGMAX:
+        actions = logits.argmax(axis=1).astype(np.uint8)  # (numpy: the first of the maxima)
+    else:
+        if uniforms is None:
+            uniforms = policy_uniform(seed, counter, env_offset + np.arange(len(x), dtype=np.uint64))
+        actions, _ = inverse_cdf(logits, uniforms, dtype)
+    mx = logits.max(axis=1)
+    lse = mx + np.log(np.exp(logits - mx[:, None]).sum(axis=1, dtype=dtype))
+    log_probs = logits[np.arange(len(x)), actions] - lse
+    return PolicyOutput(actions, values, log_probs, logits)
+
+
+def _host(t):
+    return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t
+
+
+class _MlpExtractor(nn.Module):
+    def __init__(self, obs_dim: int):
+        super().__init__()
+        self.policy_net = nn.Sequential(nn.Linear(obs_dim, HIDDEN), nn.Tanh(), nn.Linear(HIDDEN, HIDDEN), nn.Tanh())
+        self.value_net = nn.Sequential(nn.Linear(obs_dim, HIDDEN), nn.Tanh(), nn.Linear(HIDDEN, HIDDEN), nn.Tanh())
+
+
+class MlpPolicyReference(nn.Module):
+    """SB3's ActorCriticPolicy for a flat observation and Discrete(9), restated: the same parameter names
+    (mlp_extractor.policy_net.{0,2}, mlp_extractor.value_net.{0,2}, action_net, value_net), the same
+    orthogonal initialisation (gain sqrt 2 for the towers, 0.01 for action_net, 1 for value_net, zero
+    biases).  forward(obs_float [N, D]) -> (logits [N, 9], value [N])."""
+
+    def __init__(self, obs_dim: int):
+        super().__init__()
+        self.obs_dim = int(obs_dim)
+        self.mlp_extractor = _MlpExtractor(self.obs_dim)
+        self.action_net = nn.Linear(HIDDEN, N_ACTIONS)
+        self.value_net = nn.Linear(HIDDEN, 1)
+        for module, gain in ((self.mlp_extractor, math.sqrt(2)), (self.action_net, 0.01), (self.value_net, 1.0)):
+            for m in module.modules():
+                if isinstance(m, nn.Linear):
+                    nn.init.orthogonal_(m.weight, gain=gain)
+                    m.bias.data.fill_(0.0)
+
+    def forward(self, obs_float):
+        logits = self.action_net(self.mlp_extractor.policy_net(obs_float))
+        value = self.value_net(self.mlp_extractor.value_net(obs_float))
+        return logits, value[:, 0]
+
+
+class DevicePolicy:
+    """The fused acting pass on `env`'s device and stream (module text).  obs_dim defaults to the env's flat
+    observation length; seed is the seed of the policy's own uniform draws."""
+
+    def __init__(self, env, obs_dim: int | None = None, seed: int = 0):
+        if obs_dim is None:
+            from .flat import flat_dim
+            obs_dim = flat_dim(env.spec)
+        self.env = env
+        self.obs_dim = D = int(obs_dim)
+        if not 1 <= D <= _abi.PGTG_POLICY_MAX_OBS_DIM:
+            raise ValueError(f"obs_dim must be in [1, {_abi.PGTG_POLICY_MAX_OBS_DIM}]")
+        self.device = env.device
+        self.seed = int(seed)
+        self.counter = 0       # draws made so far: one per sampling act() that drew its own uniforms
+        self.env_offset = 0    # global index of env 0 (a sharded run draws what one GPU would)
+        nbytes = C.c_uint64()
+        rc = env._lib.pgtg_policy_packed_bytes(D, C.byref(nbytes))
+        if rc != _abi.PGTG_OK:
+            raise ValueError(f"pgtg_policy_packed_bytes({D}) failed ({rc})")
+        self._packed = torch.zeros(nbytes.value // 4, dtype=torch.float32, device=self.device)
+        self._loaded = False
+
+    def _fail(self, rc: int) -> None:
+        from .vector import _check
+        _check(rc, self.env._h)
+
+    def load_state_dict(self, sd) -> None:
+        """Hand a state dict of MlpPolicyReference or of SB3's MlpPolicy (tensors on any device, any
+        strides) to the kernel: float32 copies on the env's device where needed, then one launch of
+        k_policy_pack on the env's stream.  ValueError names a missing or misshapen key."""
+        shapes = weight_shapes(self.obs_dim)
+        raw, keep = _abi.PgtgPolicyWeights(obs_dim=self.obs_dim), []
+        for field, (key, _) in WEIGHT_KEYS.items():
+            if key not in sd:
+                raise ValueError(f"state dict has no {key!r}")
+            t = torch.as_tensor(sd[key])
+            if tuple(t.shape) != shapes[key]:
+                raise ValueError(f"{key!r} has shape {tuple(t.shape)}, expected {shapes[key]}")
+            t = t.detach().to(device=self.device, dtype=torch.float32).contiguous()
+            keep.append(t)
+            setattr(raw, field, t.data_ptr())
+        self.env._bind_stream()
+        rc = self.env._lib.pgtg_policy_pack(self.env._h, C.byref(raw), C.c_void_p(self._packed.data_ptr()))
+        if rc != _abi.PGTG_OK:
+            self._fail(rc)
+        self._loaded = True
+
+    def _out(self, t, n: int, dtype, name: str):
+        if t is None:
+            return torch.empty(n, dtype=dtype, device=self.device)
+        if t.dtype != dtype or t.numel() != n or not t.is_contiguous() or t.device != self.device:
+            raise ValueError(f"{name}: a contiguous {dtype} tensor of {n} values on {self.device}")
+        return t
+
+    def _launch(self, obs, mode, actions, values, log_probs, uniforms, counter) -> None:
+        if not self._loaded:
+            raise RuntimeError("load_state_dict() first")
+        if obs.dtype != torch.int8 or obs.dim() != 2 or obs.shape[1] != self.obs_dim or not obs.is_contiguous() \
+                or obs.device != self.device:
+            raise ValueError(f"obs: a contiguous int8 [N, {self.obs_dim}] tensor on {self.device}")
+        p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+        a = _abi.PgtgPolicy(n=obs.shape[0], obs_dim=self.obs_dim, obs=p(obs), packed=p(self._packed), mode=mode,
+                            seed=self.seed & ((1 << 64) - 1), counter=counter, env_offset=self.env_offset,
+                            uniforms=p(uniforms), actions=p(actions), values=p(values), log_probs=p(log_probs))
+        self.env._bind_stream()
+        rc = self.env._lib.pgtg_policy(self.env._h, C.byref(a))
+        if rc != _abi.PGTG_OK:
+            self._fail(rc)
+
+    def act(self, obs, actions=None, values=None, log_probs=None, deterministic: bool = False, uniforms=None):
+        """One launch of k_policy on obs (int8 [N, D] on the device): the sampled action (deterministic:
+        the argmax), the value and the action's log-probability of every env, written into the given [N]
+        rows (uint8, float32, float32) or into fresh tensors.  uniforms: float32 [N] in [0, 1) to sample
+        with; None draws policy_uniform(seed, counter, env_offset + e) and advances the counter."""
+        n = obs.shape[0]
+        actions = self._out(actions, n, torch.uint8, "actions")
+        values = self._out(values, n, torch.float32, "values")
+        log_probs = self._out(log_probs, n, torch.float32, "log_probs")
+        if uniforms is not None:
+            uniforms = self._out(uniforms, n, torch.float32, "uniforms")
+        self._launch(obs, ARGMAX if deterministic else SAMPLE, actions, values, log_probs, uniforms, self.counter)
+        if not deterministic and uniforms is None:
+            self.counter += 1
+        return actions, values, log_probs
+
+    def value(self, obs, out=None):
+        """V(obs) alone (the vf tower; one launch of k_policy in its value-only mode) into out or a fresh
+        float32 [N] tensor."""
+        out = self._out(out, obs.shape[0], torch.float32, "out")
+        self._launch(obs, VALUE_ONLY, None, out, None, None, 0)
+        return out

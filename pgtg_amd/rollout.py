@@ -17,6 +17,13 @@ of the HIP kernel k_gae (include/pgtg.h pgtg_gae): the time-limit bootstrap and 
     ro.finish(value_net(obs))
     for obs_b, act_b, val_b, logp_b, adv_b, ret_b in ro.get(batch_size=4096): ...
 
+With the library's own policy (pgtg_amd.policy.DevicePolicy: SB3's MlpPolicy as the HIP kernel k_policy,
+which reads obs[t] and writes the action, value and log-probability rows) the loop is the library's:
+
+    policy = DevicePolicy(env); policy.load_state_dict(module.state_dict())
+    ro.collect(policy)                                           # T x (k_policy, the tick, V(terminal_obs)), k_gae
+    for obs_b, act_b, val_b, logp_b, adv_b, ret_b in ro.get(batch_size=4096): ...
+
 While a Rollout records, it owns the handle's flat bindings (set_flat_outputs / set_flat_scalars): bind
 nothing else to them until `close()`.
 
@@ -115,6 +122,7 @@ class Rollout:
         self._started = False  # the env has been reset into obs[0]
         self._finished = False
         self._last_values = None
+        self._last_buf = None  # collect()'s V(obs[T])
 
     @property
     def nbytes(self) -> int:
@@ -188,6 +196,40 @@ class Rollout:
         if self.t < 1:
             raise RuntimeError("no step has been taken")
         self._into(self.terminal_values[self.t - 1], v)
+
+    def act(self, policy):
+        """Step t with a DevicePolicy: one launch of k_policy on obs[t] into actions[t], values[t] and
+        log_probs[t], then step() with those rows (which copies nothing), and, when the env has a time limit,
+        V(terminal_obs) into terminal_values[t] by the kernel's value-only mode.  No torch kernel."""
+        t = self.t
+        if self._dtype_code != 1:
+            raise ValueError("a policy acts on int8 rows: build the rollout with obs_dtype=torch.int8 "
+                             "(step() takes a float32 rollout's actions)")
+        if not self._started:
+            raise RuntimeError("begin() first")
+        if t >= self.n_steps:
+            raise RuntimeError(f"the rollout is full ({self.n_steps} steps): finish() and begin() again")
+        a, v, lp = policy.act(self.obs[t], self.actions[t], self.values[t], self.log_probs[t])
+        out = self.step(a, v, lp)
+        if self.env.max_episode_steps:
+            policy.value(self.terminal_obs, out=self.terminal_values[t])
+        return out
+
+    def collect(self, policy) -> None:
+        """A whole rollout with a DevicePolicy: begin() unless one is under way, T times act(), then
+        finish() on V(obs[T]) written into a buffer the rollout keeps.  Only this library's kernels are
+        launched by the steps and by finish() (the policy, the tick, the terminal values; k_gae), and nothing
+        synchronises with the host; begin() continuing a rollout copies row T to row 0 as it always did."""
+        import torch
+        if self._dtype_code != 1:
+            raise ValueError("a policy acts on int8 rows: build the rollout with obs_dtype=torch.int8")
+        if not self._started or self._finished or self.t >= self.n_steps:
+            self.begin()
+        while self.t < self.n_steps:
+            self.act(policy)
+        if self._last_buf is None:
+            self._last_buf = torch.zeros(self.num_envs, dtype=torch.float32, device=self.device)
+        self.finish(policy.value(self.obs[self.n_steps], out=self._last_buf))
 
     def finish(self, last_values) -> None:
         """advantages and returns of the whole rollout in one launch of k_gae; last_values = V(obs[T])."""
