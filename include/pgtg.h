@@ -234,12 +234,19 @@ int pgtg_load_state(pgtg_handle* h, const void* buf, uint64_t bytes);
  * of the handle's per-env state sections (everything in the state blob but the batch-wide counters),
  * allocated zeroed for `slots` envs; `slots` need not be the handle's batch size.  It records the
  * handle's configuration hash, the shape fields of the blob header (tile count, car capacity and slots,
- * plan stride, spawner capacity, visited words, ring entry words), the map ring's depth and the device:
+ * plan stride, spawner capacity, visited words, ring entry words), the map ring's layout and the device:
  * pgtg_snapshot_save / _load accept ANY handle on that device for which all of these are equal -- a
  * snapshot saved from one handle loads into another handle of another batch size -- and refuse every
- * other handle with PGTG_E_INVALID and a message on that handle, launching nothing.  (The ring depth
- * follows the map-queue step kernel, k_envq 2 / k_envb 3, which tune_queue_mode 0 picks from the batch
- * size: fix it with tune_queue_mode to share snapshots between batches of very different sizes.)
+ * other handle with PGTG_E_INVALID and a message on that handle, launching nothing.  (The ring layout
+ * follows the map-queue step kernel, which tune_queue_mode 0 picks from the batch size: k_envq keeps three
+ * 128-byte-aligned slots per env (one more than before), the live episode's tile plan in one of them, and
+ * no separate plan row (device memory per env: one slot more, the row less.  A slot is the plan's 16-byte
+ * quads plus 16 bytes in whole 128-byte lines, a row the plan in whole lines, or 32 bytes below 16 tiles:
+ * equal for 16 to 56 tiles (5x5: 128 and 128) and for 9x9 (256 and 256), +96 bytes below 16 tiles, +128
+ * bytes where the 16 bytes open another line, e.g. 57 to 64 tiles),
+ * k_envb three queued maps beside the plan row; state blobs of one are refused by the other in the same
+ * way.  Fix it with tune_queue_mode to share snapshots between batches of very different sizes.  k_envq
+ * handles hold at most 2^30 envs: PGTG_E_UNSUPPORTED from pgtg_create beyond.)
  *   save: env env_idx_dev[k] of h -> slot slot_idx_dev[k];   load: slot slot_idx_dev[k] -> env
  *   env_idx_dev[k] of h, for k < count.  Index arrays are uint32 device arrays; NULL = the identity k.
  * One launch of k_state_copy (after the pending map-ring refills, as before pgtg_dump_state) on the

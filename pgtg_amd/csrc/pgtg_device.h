@@ -167,7 +167,8 @@ struct DevState {
   uint64_t n;
   EnvRec* rec;
   uint64_t* seed;
-  uint16_t* plan;         // [n][plan_stride]
+  uint16_t* plan;         // [n][plan_stride], or null: k_envq handles keep an env's plan in the cur slot of
+                          // its map ring (pgtg_env.hip plan_row)
   DevStream car, ice, broken, sand;
   uint32_t* visited;      // [n][vis_words] or null
   // traffic: one bank of car slots per env in id order (= the reference's list order), slot-major /
@@ -196,11 +197,13 @@ struct DevState {
   uint32_t sp_pitch, fresh_dw, fresh_occ;
   uint32_t* tr_list;      // [n] envs k_env reset this launch (k_traffic's work list)
   uint32_t* tr_count;     // [2] list lengths, alternating launches
-  // map queue (k_envq): per env a ring of kQueueDepth pre-generated episode maps, entry = plan
-  // words then {px | py<<16, sg, path_len | error<<16, spawn tag}; qstate = head slot | kQueueStale
+  // map queue (k_envq): per env a ring of kQueueDepth slots, entry = plan words then {px | py<<16, sg,
+  // path_len | error<<16, spawn tag}: the live episode's plan (cur) and the next two episodes' maps
+  // (head, spare); qstate = cur slot | head slot << 2 | kQueueStale.  (k_envb: three queued maps,
+  // qstate = held | head << 2.)
   uint32_t* qbuf;         // [n][kQueueDepth][qrec_dw] or null
   uint8_t* qstate;        // [n] or null
-  uint2* qreq;            // [2][grid][cap] refill requests {env << 1 | slot, spawn counter} per k_envq
+  uint2* qreq;            // [2][grid][cap] refill requests {env << 2 | slot, spawn counter} per k_envq
                           // workgroup, alternating launches
   uint2* qovf;            // [2][8][cap] one-round launches: the requests beyond a workgroup's first 64
   uint32_t* qctr;         // the lists' lengths, block counters, overflow lengths and heads (kQctr*)

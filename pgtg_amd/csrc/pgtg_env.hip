@@ -183,8 +183,40 @@ __device__ __forceinline__ uint32_t plan_word_mask(const DevCfg& c, int word) {
   const int t0 = 2 * word;
   return t0 + 1 < c.nt ? ~0u : (t0 < c.nt ? 0xffffu : 0u);
 }
-// The env's LDS plan row (pdw words) back to its HBM tile plan (plan_stride u16 words), padding as 0.
+constexpr int kQueueDepth = 3;   // ring slots per env of k_envq: the live episode's map (cur) and the next two's
+// qstate of a k_envq handle: cur slot | head slot << 2 (| kQueueStale); the third slot is the spare
+// (two bits as a slot index: never outside the ring, whatever the byte holds)
+__host__ __device__ inline uint32_t queue_slot(uint32_t bits) { return (bits & 3u) < 2u ? (bits & 3u) : 2u; }
+__host__ __device__ inline uint32_t queue_cur(uint32_t qs) { return queue_slot(qs); }
+__host__ __device__ inline uint32_t queue_head(uint32_t qs) { return queue_slot(qs >> 2); }
+// the spare of a ring whose cur and head differ (else cur's successor's successor: still a slot)
+__host__ __device__ inline uint32_t queue_spare(uint32_t qc, uint32_t qh) { return qc != qh ? 3u - qc - qh : (qc + 2u) % 3u; }
+// Where env i's live tile plan is: its row of S.plan, or, in a k_envq handle (which has no S.plan), the
+// ring slot that holds its episode (cur).  Every reader and writer of an env's plan goes through here.
+// SLOT is a compile-time choice in the step kernels (k_env has an instance of its own for k_envq handles,
+// so that its code for every other handle is what it was); k_squares tests S.plan at run time.
+template <bool SLOT>
+__device__ __forceinline__ uint16_t* plan_row(const DevCfg& c, const DevState& S, uint64_t i) {
+  if (!SLOT) return S.plan + i * (uint64_t)c.plan_stride;
+  return reinterpret_cast<uint16_t*>(S.qbuf + (i * kQueueDepth + queue_cur(S.qstate[i])) * (uint64_t)c.qrec_dw);
+}
+// An LDS plan row (pdw words) into the first nq 16-byte quads of dst, padding as 0.
+__device__ __forceinline__ void store_plan_quads(const DevCfg& c, uint4* dstp, int nq, const uint32_t* pw, int pdw) {
+  for (int k = 0; k < nq; k++) {
+    uint32_t wv[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) wv[j] = (k * 4 + j < pdw) ? pw[k * 4 + j] & plan_word_mask(c, k * 4 + j) : 0u;
+    dstp[k] = make_uint4(wv[0], wv[1], wv[2], wv[3]);
+  }
+}
+// The env's LDS plan row (pdw words) back to its HBM tile plan: the whole row of plan_stride u16 words,
+// or the whole cur slot (its meta words, unused while the episode is live, as 0), padding as 0.
+template <bool SLOT>
 __device__ __forceinline__ void store_plan_row(const DevCfg& c, const DevState& S, uint64_t i, const uint32_t* pw, int pdw) {
+  if (SLOT) {
+    store_plan_quads(c, reinterpret_cast<uint4*>(plan_row<true>(c, S, i)), c.qrec_dw / 4, pw, pdw);
+    return;
+  }
   uint4* dstp = reinterpret_cast<uint4*>(S.plan + i * (uint64_t)c.plan_stride);
   for (int k = 0; k < c.plan_stride / 8; k++) {
     uint32_t wv[4];
@@ -2787,7 +2819,6 @@ __host__ __device__ inline uint64_t queue_req_cap(uint64_t nblk, uint64_t grid, 
   return c < (uint64_t)kQueueLanes ? (uint64_t)kQueueLanes : c;  // (the helper reads its first kQueueLanes ahead)
 }
 constexpr uint64_t kStaggerMaxTicks = 20000;  // 200 us of 100 MHz wall clock: a bound, never reached
-constexpr int kQueueDepth = 2;   // queued maps per env (a ring: the next two episodes') of k_envq
 constexpr int kBlockDepth = 3;   // of k_envb (the rings refilled per block)
 constexpr uint32_t kQueueStale = 0x80u;  // qstate flag: the ring's entries are not this env's (k_qfill)
 constexpr int kViewDw = 8;       // k_envq with <= 32 envs: an env's view words for the image builders
@@ -2935,7 +2966,7 @@ __device__ __forceinline__ void stagger_record(const Lds& L, const DevState& S, 
   if (L.stagger && blockIdx.x == 0 && threadIdx.x == 0) S.wg_ticks[0] = wall_clock64() - t0;
 }
 
-template <bool TR, bool BIG>
+template <bool TR, bool BIG, bool SLOT = false>
 __global__ void __launch_bounds__(kBlock, TR ? 3 : 4) k_env(const DevCfg* __restrict__ cfg, const Tables* __restrict__ gtab,
                                                  DevState S, const uint8_t* __restrict__ actions,
                                                  const uint8_t* __restrict__ mask, PgtgOutputs out, int mode, Lds L,
@@ -2995,7 +3026,7 @@ __global__ void __launch_bounds__(kBlock, TR ? 3 : 4) k_env(const DevCfg* __rest
       ts.fresh = (tr4.w & kTrafFresh) ? 1u : 0u;
       occ_valid = (tr4.w & kTrafOccValid) != 0u;
     }
-    stage_plan<BIG>(S.plan + i * (uint64_t)c.plan_stride, c.plan_dq, plan_w, L.plan_stride_dw);
+    stage_plan<BIG>(plan_row<SLOT>(c, S, i), c.plan_dq, plan_w, L.plan_stride_dw);
   }
   for (int k = tid; k < L.lm_words; k += kBlock) lm[k] = 0u;
   lds_barrier();  // sT ready
@@ -3079,7 +3110,7 @@ __global__ void __launch_bounds__(kBlock, TR ? 3 : 4) k_env(const DevCfg* __rest
       occ_valid = (TR && c.need_car) && !occ_sat && err == 0;
       const bool done = (v.flags & (kFlagTerminated | kFlagTruncated)) != 0;
       // BIG maps keep the used subgoals in the plan: the row goes back to HBM unless the env resets now
-      if (BIG && res.plan_dirty && !(done && c.autoreset && err == 0)) store_plan_row(c, S, i, plan_w, L.plan_stride_dw);
+      if (BIG && res.plan_dirty && !(done && c.autoreset && err == 0)) store_plan_row<SLOT>(c, S, i, plan_w, L.plan_stride_dw);
       if (out.reward) out.reward[i] = res.reward;
       if (out.cost) out.cost[i] = res.cost;
       if (out.terminated) out.terminated[i] = (v.flags & kFlagTerminated) ? 1 : 0;
@@ -3172,7 +3203,7 @@ __global__ void __launch_bounds__(kBlock, TR ? 3 : 4) k_env(const DevCfg* __rest
       vv.spawn = xw[0];
       TrafState tw{0, 0, 0, 0};
       const int e2 = env_reset<TR, BIG>(c, S, iw, vv, reinterpret_cast<uint16_t*>(pw), tw);
-      store_plan_row(c, S, iw, pw, L.plan_stride_dw);
+      store_plan_row<SLOT>(c, S, iw, pw, L.plan_stride_dw);
       xw[0] = ((uint32_t)vv.px & 0xffffu) | ((uint32_t)vv.py << 16);
       xw[1] = vv.sg;
       xw[2] = vv.path_len | (uint32_t)(-e2) << 16;
@@ -3199,7 +3230,7 @@ __global__ void __launch_bounds__(kBlock, TR ? 3 : 4) k_env(const DevCfg* __rest
     int e2 = env_reset<TR, BIG>(c, S, i, v, pl.p, ts);
     if (e2) err = e2;
     tr_push = (TR && c.need_car) && e2 == 0;
-    store_plan_row(c, S, i, plan_w, L.plan_stride_dw);
+    store_plan_row<SLOT>(c, S, i, plan_w, L.plan_stride_dw);
   }
   STAMP(4);
   if (live) {
@@ -3211,7 +3242,8 @@ __global__ void __launch_bounds__(kBlock, TR ? 3 : 4) k_env(const DevCfg* __rest
                                (occ_valid && !reset_now ? kTrafOccValid : 0u) | (ts.fresh ? kTrafFresh : 0u));
     }
     if (mode != MODE_OBSERVE || err) S.err[i] = (uint8_t)(-err);
-    if (S.qstate && reset_now) S.qstate[i] = (uint8_t)kQueueStale;  // maps generated here: the queued ones are stale
+    // maps generated here: the queued ones are stale (a k_envq handle's cur slot, which holds the new plan, stays)
+    if (S.qstate && reset_now) S.qstate[i] = (uint8_t)(SLOT ? (queue_cur(S.qstate[i]) | kQueueStale) : kQueueStale);
   }
   if (TR && c.need_car) {
     // k_traffic's work list: one wave-aggregated atomic per wave
@@ -3346,12 +3378,20 @@ __device__ __forceinline__ void sub_barrier(uint32_t* ctr, uint32_t target) {
 // workgroups resident at once; each takes env block blockIdx.x, then the next free one from a counter
 // (fetched one block ahead), until none is left.  Its env and writer waves step a block, write the
 // terminal observations, take the ring heads of the envs that finished -- requesting the
-// next-but-one episode's map for the slot taken, in the workgroup's own list -- and write the new
+// next-but-one episode's map for the slot freed, in the workgroup's own list -- and write the new
 // observations, synchronising among themselves only.  Its helper wave (wave `env_waves`, the first
 // without env slots) meanwhile generates the maps its workgroup requested in the previous launch,
-// kQueueLanes at a time, so that neither role waits for the other at a block's end.  A request made
-// in launch t is served in launch t + 1 and its entry taken in t + 2 at the earliest: two entries
-// per env suffice, and no entry is written while it can be read.
+// kQueueLanes at a time, so that neither role waits for the other at a block's end.
+// An env's ring has three slots with rotating roles (qstate = cur | head << 2): cur holds the live
+// episode's tile plan -- there is no other copy: staging reads it, BIG maps mark their used subgoals
+// in it, every other reader finds it through plan_row -- head the entry for the env's spawn counter k0,
+// and the third, the spare, the entry for k0 + 5, ready or being made.  A reset changes nothing but the
+// roles: the old cur is freed and requested for k0 + 10, head becomes cur (its plan goes to the LDS row,
+// its meta words to the env record; no plan store to HBM), the spare becomes head.  A request made in
+// launch t is served in launch t + 1 and its entry taken in t + 2 at the earliest, and the helper only
+// ever writes a slot that was neither cur nor head when its launch began: no entry is written while it
+// can be read.  The next block's qstate bytes are fetched one block ahead (the block index is published
+// after the step), so that the plan's address does not wait for a load of its own at staging.
 // (One shared request list instead: 497 vs 456 us per 1 048 576-env launch, its counter a hot spot on
 // every env wave's path; static blocks blockIdx.x + k * gridDim.x: 455 us against the counter's 424.)
 // The map-queue step's observation images.  With <= 32 envs per workgroup they all sit in wave 0
@@ -3409,12 +3449,12 @@ __device__ __forceinline__ void group_obs(const DevCfg& c, const DevState& S, co
   }
 }
 
-// A reset's ring take: the head entry of env i's ring (slot qh, made for spawn counter k0) becomes its
-// episode -- the tile plan into its HBM row and its LDS row, the obstacle streams of the episode, and
+// k_envb's ring take (k_envq moves roles instead and copies nothing): the head entry of env i's ring
+// (slot qh, made for spawn counter k0) becomes its episode -- the tile plan into its HBM row and its LDS row, the obstacle streams of the episode, and
 // {px | py << 16, start/goal word, path length | error << 16} returned (env_reset without the generation).
 template <bool BIG>
 __device__ __forceinline__ uint3 ring_take(const DevCfg& c, const DevState& S, const Lds& L, uint64_t i, uint32_t qh,
-                                           uint32_t k0, uint32_t* plan_w, int pdw, int depth = kQueueDepth) {
+                                           uint32_t k0, uint32_t* plan_w, int pdw, int depth) {
   const uint4* q4 = reinterpret_cast<const uint4*>(S.qbuf + (i * (uint64_t)depth + qh) * (uint64_t)c.qrec_dw);
   uint4* dstp = reinterpret_cast<uint4*>(S.plan + i * (uint64_t)c.plan_stride);
   // all loads of the entry first: a load after a store to S.plan (which the compiler cannot
@@ -3444,9 +3484,8 @@ __device__ __forceinline__ uint3 ring_take(const DevCfg& c, const DevState& S, c
     if (c.need_broken) stream_store_all(S.broken, i, ss_child(sp, k0 + 3u));
     if (c.need_sand) stream_store_all(S.sand, i, ss_child(sp, k0 + 4u));
   }
-  // the entry was generated for this episode (spawn counter k0): k_envq serves every request of a
-  // launch in the next one and its ring holds two entries, k_envb refills every empty head before the
-  // take, so it always is -- a mismatch is reported as a device error, never used
+  // the entry was generated for this episode (spawn counter k0): k_envb refills every empty head before
+  // the take, so it always is -- a mismatch is reported as a device error, never used
   const int e2 = (meta.w != queue_tag(k0) && !ABLATE(L, 1 | 16)) ? PGTG_E_DEVICE : -(int)(meta.z >> 16);
   return make_uint3(meta.x, meta.y, (meta.z & 0xffffu) | (uint32_t)(-e2) << 16);
 }
@@ -3484,6 +3523,9 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
     r0 = req_old[lane];  // (cap >= kQueueLanes: inside the list, used only below cnt)
   }
   if (blockIdx.x == 0 && tid < 8) S.qctr[kQctrOvfLen + ((set_new + 1u) % 3u) * 8u + tid] = 0u;  // (the launch after next's)
+  // the first block's qstate bytes, issued before the tables are staged (a later block's: one block ahead)
+  uint32_t qs_nx = 0;
+  if (tid < L.envs && (uint64_t)blockIdx.x * L.envs + tid < S.n) qs_nx = S.qstate[(uint64_t)blockIdx.x * L.envs + tid];
   const int pdw = L.plan_stride_dw;
   stage_tables(gtab, false);  // (the map queue runs without lane channels: no sTX reference here)
   uint32_t* st = lds + L.envs * (pdw + L.scratch_dw + L.traf_dw + L.hist_dw);
@@ -3502,6 +3544,11 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
     *qn = 0u;
   }
   lds_barrier();  // tables, counters
+  // The qstate byte is wanted in its register before a block's staging begins.  Loads and stores retire
+  // through one in-order counter: a wait for the byte at staging would also wait for the previous block's
+  // image stores, and only then could the plan loads go out.  So the wait is placed where it costs
+  // nothing -- here behind the table staging, and in the loop behind the take, whose own loads are younger.
+  asm volatile("" : "+v"(qs_nx));
 
   if (wave == gen_wave) {
     STAMP(1);
@@ -3538,8 +3585,8 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
         ovs += oth;
         if ((uint32_t)lane < own + oth) {
           const uint2 r = (uint32_t)lane >= own ? ovf[ob + (lane - own)] : base == 0 ? r0 : req_old[base + lane];
-          const uint64_t ie = r.x >> 1;
-          gen_queue_entry<BIG>(c, S, ie, r.y, gplan, pdw, S.qbuf + (ie * kQueueDepth + (r.x & 1u)) * (uint64_t)c.qrec_dw,
+          const uint64_t ie = r.x >> 2;
+          gen_queue_entry<BIG>(c, S, ie, r.y, gplan, pdw, S.qbuf + (ie * kQueueDepth + queue_slot(r.x)) * (uint64_t)c.qrec_dw,
                                ABLATE(L, 16), false);
         }
         if (base + kQueueLanes >= cnt) break;
@@ -3550,8 +3597,8 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
         ovs += m;
         if ((uint32_t)lane < m) {
           const uint2 r = ovf[st0 + lane];
-          const uint64_t ie = r.x >> 1;
-          gen_queue_entry<BIG>(c, S, ie, r.y, gplan, pdw, S.qbuf + (ie * kQueueDepth + (r.x & 1u)) * (uint64_t)c.qrec_dw,
+          const uint64_t ie = r.x >> 2;
+          gen_queue_entry<BIG>(c, S, ie, r.y, gplan, pdw, S.qbuf + (ie * kQueueDepth + queue_slot(r.x)) * (uint64_t)c.qrec_dw,
                                ABLATE(L, 16), false);
         }
       }
@@ -3586,13 +3633,13 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
     const uint64_t i = env0 + slot;
     const bool live = env_wave && slot < nb;
     EnvView v{};
-    uint32_t qh = 0;
+    const uint32_t qs = qs_nx;  // (fetched during the previous block)
+    const auto ring_slot = [&](uint32_t s) { return S.qbuf + (i * kQueueDepth + s) * (uint64_t)c.qrec_dw; };
     int act = 0;
     if (live) {
       v = rec_load(S.rec, i);
-      qh = S.qstate[i] & 1u;
       act = actions[i];  // issued with the staging loads, not on the step's chain
-      stage_plan<BIG>(S.plan + i * (uint64_t)c.plan_stride, c.plan_dq, plan_w, pdw);
+      stage_plan<BIG>(reinterpret_cast<const uint16_t*>(ring_slot(queue_cur(qs))), c.plan_dq, plan_w, pdw);  // the cur slot
     }
     for (int k = rank; k < L.lm_words; k += nthr) lm[k] = 0u;
     sub_barrier(ctr, bar += (uint32_t)np);  // plans, line mask (and the last block's images written)
@@ -3612,7 +3659,8 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
       if (out.truncated) out.truncated[i] = (v.flags & kFlagTruncated) ? 1 : 0;
       if (out.braking) out.braking[i] = 0;
       my_sel = (done && c.autoreset && err == 0) ? 1 : 0;
-      if (BIG && res.plan_dirty && !my_sel) store_plan_row(c, S, i, plan_w, pdw);  // used subgoals (kPlanUsed)
+      if (BIG && res.plan_dirty && !my_sel)  // used subgoals (kPlanUsed), into the cur slot's plan quads
+        store_plan_quads(c, reinterpret_cast<uint4*>(ring_slot(queue_cur(qs))), c.plan_dq, plan_w, pdw);
       if (lm && my_sel && out.final_obs) mark_lines(lm, out.final_obs + env0 * (uint64_t)c.obs_bytes, (uint32_t)slot, (uint32_t)c.obs_bytes);
       STAMP(23);
     }
@@ -3625,40 +3673,33 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
     if (env_wave) sel[slot] = my_sel;
     const uint64_t rm = __ballot(my_sel == 1);
     if (env_wave && lane == 0 && rm) atomicAdd(&S.counters[1], (unsigned long long)__popcll(rm));
+    if (tid == 0) *nxt = got;  // (read from here to the block's end; rewritten after the next block's first barrier)
     STAMP(2);
     STAMP(28);
     sub_barrier(ctr, bar += (uint32_t)np);
     STAMP(29);
+    // the next block's qstate bytes, a block ahead: their latency passes behind this block's writes,
+    // and the next staging computes its plan address from a register
+    {
+      const uint32_t g = *nxt;
+      const uint64_t ni = ((uint64_t)gridDim.x + g) * (uint64_t)L.envs + (uint64_t)slot;
+      qs_nx = 0;
+      if (g != 0xffffffffu && slot < L.envs && ni < S.n) qs_nx = S.qstate[ni];
+    }
     if (out.final_obs && !ABLATE(L, 2))
       write_obs(out.final_obs + env0 * (uint64_t)c.obs_bytes, (uint32_t)nb, (uint32_t)c.obs_bytes, st, sel, rank, nthr, lm);
     STAMP(3);
     sub_barrier(ctr, bar += (uint32_t)np);  // terminal images written before they are rebuilt
     const bool reset_now = my_sel != 0;
     const uint32_t k0 = v.spawn;
+    const uint32_t qc = queue_cur(qs), qh = queue_head(qs);
     if (reset_now) {  // the ring's head becomes the episode (env_reset without the generation)
-      const uint4* q4 = reinterpret_cast<const uint4*>(S.qbuf + (i * kQueueDepth + qh) * (uint64_t)c.qrec_dw);
-      uint4* dstp = reinterpret_cast<uint4*>(S.plan + i * (uint64_t)c.plan_stride);
-      // all loads of the entry first: a load after a store to S.plan (which the compiler cannot
-      // tell apart from the queue) would wait for the one before it, one HBM latency per 16 bytes
+      // its plan into the LDS row, its meta words into the env record: the entry stays where it is, as
+      // the cur slot (no copy of the plan in HBM)
+      const uint4* q4 = reinterpret_cast<const uint4*>(ring_slot(qh));
       const int nq = c.plan_dq;  // 16-byte words of the tile plan (<= 8 unless BIG)
       const uint4 meta = q4[nq];
-      for (int k0q = 0; k0q < (BIG ? nq : 1); k0q += 8) {
-        uint4 qw[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) qw[k] = q4[k0q + k < nq ? k0q + k : k0q];  // unconditional: registers, not scratch
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-          if (k0q + k < nq) {
-            if (!ABLATE(L, 32)) dstp[k0q + k] = qw[k];
-            const uint32_t wv[4] = {qw[k].x, qw[k].y, qw[k].z, qw[k].w};
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-              if ((k0q + k) * 4 + j < pdw) plan_w[(k0q + k) * 4 + j] = wv[j];
-          }
-        }
-      }
-      if (!ABLATE(L, 32))
-        for (int k = nq; k < c.plan_stride / 8; k++) dstp[k] = make_uint4(0u, 0u, 0u, 0u);  // the row's whole lines
+      stage_plan<BIG>(reinterpret_cast<const uint16_t*>(q4), nq, plan_w, pdw);
       if (c.need_ice || c.need_broken || c.need_sand) {
         SeedPool sp = ss_pool(S.seed[i]);
         if (c.need_ice) stream_store_all(S.ice, i, ss_child(sp, k0 + 2u));
@@ -3676,8 +3717,8 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
       v.px = (int)(int16_t)(meta.x & 0xffffu);
       v.py = (int)(int16_t)(meta.x >> 16);
       // the entry was generated for this episode (spawn counter k0): every launch serves all of the
-      // previous launch's requests and the ring holds two entries, so it always is -- a mismatch is
-      // reported as a device error, never used
+      // previous launch's requests and the ring holds the next two episodes' entries beside the live
+      // one, so it always is -- a mismatch is reported as a device error, never used
       const int e2 = (meta.w != queue_tag(k0) && !ABLATE(L, 1 | 16)) ? PGTG_E_DEVICE : -(int)(meta.z >> 16);
       if (e2) err = e2;
       if (S.visited && e2 == 0) {
@@ -3687,8 +3728,9 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
         vis[b >> 5] |= 1u << (b & 31);
       }
     }
+    asm volatile("" : "+v"(qs_nx));  // (the next block's qstate byte has arrived: see above the loop)
     STAMP(4);
-    // refill request: the next-but-one episode's map (spawn counter k0 + 10) into the slot just taken
+    // refill request: the next-but-one episode's map (spawn counter k0 + 10) into the slot freed
     const uint64_t rb = __ballot(reset_now);
     if (rb) {
       uint32_t base = 0;
@@ -3704,12 +3746,13 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
       }
       if (reset_now) {
         const uint32_t p = base + (uint32_t)__popcll(rb & ((1ull << lane) - 1ull));
-        const uint2 r = make_uint2((uint32_t)i << 1 | qh, k0 + 10u);
+        const uint2 r = make_uint2((uint32_t)i << 2 | qc, k0 + 10u);  // (the slot freed: the old cur)
         if (one_round && p >= (uint32_t)kQueueLanes)
           S.qovf[((uint64_t)par * 8u + ox) * ocap + obase + (p - max(base, (uint32_t)kQueueLanes))] = r;
         else
           req_new[p] = r;
-        S.qstate[i] = (uint8_t)(qh ^ 1u);  // (every env's byte instead: 403.3 vs 401.4 us)
+        // the roles rotate: head -> cur, spare -> head  (every env's byte instead: 403.3 vs 401.4 us)
+        S.qstate[i] = (uint8_t)(qh | queue_spare(qc, qh) << 2);
       }
     }
     if (live) {
@@ -3722,13 +3765,12 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
       group_obs<BIG>(c, S, v, reset_now, st, oi, L, wave, lane, ctr, bar, np, rank, vw, false);
       if (reset_now) write_small_outputs(c, out, i, v, oi, false);
     }
-    if (tid == 0) *nxt = got;
     STAMP(30);
     sub_barrier(ctr, bar += (uint32_t)np);
     STAMP(31);
     if (tid == 0)  // (every request of the block is in)
       S.qctr[par * gridDim.x + blockIdx.x] = one_round ? min(*qn, (uint32_t)kQueueLanes) : *qn;
-    const uint32_t g = *nxt;  // (written before the last barrier, rewritten after the next block's first)
+    const uint32_t g = *nxt;  // (published after the step, rewritten after the next block's first barrier)
     if (out.obs && !ABLATE(L, 4))
       write_obs(out.obs + env0 * (uint64_t)c.obs_bytes, (uint32_t)nb, (uint32_t)c.obs_bytes, st, nullptr, rank, nthr);
     if (tid == 0) atomicAdd(&S.counters[0], (unsigned long long)nb);
@@ -3884,7 +3926,7 @@ __global__ void __launch_bounds__(kBlock, 4) k_envb(const DevCfg* __restrict__ c
     if (out.truncated) out.truncated[i] = (v.flags & kFlagTruncated) ? 1 : 0;
     if (out.braking) out.braking[i] = 0;
     my_sel = (done && c.autoreset && err == 0) ? 1 : 0;
-    if (BIG && res.plan_dirty && !my_sel) store_plan_row(c, S, i, plan_w, pdw);  // used subgoals (kPlanUsed)
+    if (BIG && res.plan_dirty && !my_sel) store_plan_row<false>(c, S, i, plan_w, pdw);  // used subgoals (kPlanUsed)
     if (lm && my_sel && out.final_obs) mark_lines(lm, out.final_obs + env0 * (uint64_t)c.obs_bytes, (uint32_t)slot, (uint32_t)c.obs_bytes);
     STAMP(23);
   }
@@ -3969,8 +4011,8 @@ __global__ void __launch_bounds__(kBlock, 4) k_envb(const DevCfg* __restrict__ c
 
 // Fill every env's map ring: after a reset launch (whose k_env generated the current episodes' maps
 // and marked the reset envs' rings stale), a state dump (the requests still pending) or a change of
-// step kernel.  One lane per env checks both entries' spawn tags against the env's next two episodes
-// (spawn counters s and s + 5, the head first) and generates the ones that do not match -- the maps
+// step kernel.  One lane per env checks the head's and the spare's spawn tags against the env's next two
+// episodes (spawn counters s and s + 5; the cur slot, the live plan, is left alone) and generates the ones that do not match -- the maps
 // k_envq's helpers would generate -- so that the step launches start with full rings.  The entries
 // are a function of (seed, spawn counter) alone: results are unchanged.
 template <bool BIG>
@@ -3984,19 +4026,23 @@ __global__ void __launch_bounds__(kBlock) k_qfill(const DevCfg* __restrict__ cfg
   uint32_t made = 0;
   if (i < S.n) {
     const uint32_t qs = S.qstate[i];
-    const bool stale = (qs & kQueueStale) != 0;
-    const uint32_t qh = stale ? 0u : (qs & 1u);
+    // the cur slot holds the live plan (a reset launch's k_env wrote it there) and keeps its place; a
+    // stale ring's head and spare are the two slots after it
+    const uint32_t qc = queue_cur(qs);
+    const bool stale = (qs & kQueueStale) != 0 || queue_head(qs) == qc || ((qs >> 2) & 3u) == 3u;
+    const uint32_t qh = stale ? (qc + 1u) % 3u : queue_head(qs);
+    const uint32_t qsp = queue_spare(qc, qh);
     const uint32_t spawn = S.rec[i].b.y;  // EnvRec w5
     const int tag_w = c.plan_dq * 4 + 3;
     uint16_t* plan = reinterpret_cast<uint16_t*>(lds + threadIdx.x * pdw);
-    for (uint32_t l = 0; l < (uint32_t)kQueueDepth; l++) {
-      uint32_t* dst = S.qbuf + (i * kQueueDepth + (qh ^ l)) * (uint64_t)c.qrec_dw;
+    for (uint32_t l = 0; l < 2u; l++) {
+      uint32_t* dst = S.qbuf + (i * kQueueDepth + (l == 0 ? qh : qsp)) * (uint64_t)c.qrec_dw;
       if (stale || dst[tag_w] != queue_tag(spawn + 5u * l)) {
         gen_queue_entry<BIG>(c, S, i, spawn + 5u * l, plan, pdw, dst);
         made++;
       }
     }
-    if (stale) S.qstate[i] = 0;
+    if (stale) S.qstate[i] = (uint8_t)(qc | qh << 2);
   }
   // maps generated (S.counters[2]): one atomic per wave
   const uint32_t wsum = (uint32_t)__popcll(__ballot(made & 1u)) + 2u * (uint32_t)__popcll(__ballot(made & 2u));
@@ -4178,7 +4224,8 @@ __global__ void __launch_bounds__(kBlock) k_squares(const DevCfg* __restrict__ c
     for (int k = tid; k < (int)(sizeof(TablesHead) / 4); k += blockDim.x) dstt[k] = src[k];
     uint32_t* dstx = reinterpret_cast<uint32_t*>(&sTX);
     for (int k = tid; k < (int)(sizeof(TablesTail) / 4); k += blockDim.x) dstx[k] = src[kTabHead / 4 + k];
-    for (int t = tid; t < c.nt; t += blockDim.x) plan_s[t] = S.plan[i * (uint64_t)c.plan_stride + t];
+    const uint16_t* prow = S.plan ? plan_row<false>(c, S, i) : plan_row<true>(c, S, i);
+    for (int t = tid; t < c.nt; t += blockDim.x) plan_s[t] = prow[t];
   }
   __syncthreads();
   const EnvView v = rec_load(S.rec, i);
@@ -4587,6 +4634,7 @@ struct pgtg_handle {
   uint64_t q_grid = 0;
   // map-queue step kernel, fixed at create: 1 k_envb (<= 2 rounds of workgroups), 0 k_envq, -1 not yet
   int q_block = -1;
+  bool slot_plan = false;  // a k_envq handle: no S.plan, an env's plan is the cur slot of its ring
   int tune_queue_mode = 0;  // PgtgConfig.tune_queue_mode
   // FlattenObservation rows after every launch (pgtg_set_flat_outputs): k_flatten's arguments
   FlatArgs flat{};
@@ -4609,6 +4657,10 @@ struct pgtg_handle {
 // them: k_envq for steps when the map queue is on, else k_env<false>; BIG: maps of > 64 tiles).
 static const void* step_fn(const pgtg_handle* h, int mode) {
   const bool big = h->hcfg.nt > kSmallTiles;
+  if (h->slot_plan) {  // a k_envq handle: the k_env instances that find an env's plan in its ring slot
+    if (h->hcfg.n_rules > 0) return big ? (const void*)k_env<true, true, true> : (const void*)k_env<true, false, true>;
+    if (mode != MODE_STEP || !h->L.queue) return big ? (const void*)k_env<false, true, true> : (const void*)k_env<false, false, true>;
+  }
   if (h->hcfg.need_car || h->hcfg.n_rules > 0) return big ? (const void*)k_env<true, true> : (const void*)k_env<true, false>;
   if (mode == MODE_STEP && h->L.queue) {
     if (h->q_block == 1) return big ? (const void*)k_envb<true> : (const void*)k_envb<false>;
@@ -4617,7 +4669,7 @@ static const void* step_fn(const pgtg_handle* h, int mode) {
   return big ? (const void*)k_env<false, true> : (const void*)k_env<false, false>;
 }
 
-// entries per env ring of this handle's map queue (k_envb 3, k_envq 2)
+// slots per env ring of this handle's map queue (three in both kernels; k_envq's hold the live plan too: snapshot_shape)
 static int queue_depth(const pgtg_handle* h) { return h->q_block == 1 ? kBlockDepth : kQueueDepth; }
 
 static thread_local std::string g_create_err;
@@ -5103,7 +5155,9 @@ static int choose_launch(pgtg_handle* h, bool allow_queue) {
   if (h->lds > 64 * 1024) {
     const void* fns[] = {(const void*)k_env<true, false>, (const void*)k_env<false, false>, (const void*)k_envq<false>,
                          (const void*)k_env<true, true>, (const void*)k_env<false, true>, (const void*)k_envq<true>,
-                         (const void*)k_envb<false>, (const void*)k_envb<true>};
+                         (const void*)k_envb<false>, (const void*)k_envb<true>,
+                         (const void*)k_env<true, false, true>, (const void*)k_env<false, false, true>,
+                         (const void*)k_env<true, true, true>, (const void*)k_env<false, true, true>};
     for (const void* f : fns) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds);
   }
   // first-round start offsets (stagger_start) for the launches without traffic
@@ -5172,7 +5226,6 @@ int pgtg_create(const PgtgConfig* cfg, uint64_t n_envs, int32_t device, pgtg_han
   ALLOC(h->dcfg, 1);
   ALLOC(S.rec, n);
   ALLOC(S.seed, n);
-  ALLOC(S.plan, n * (uint64_t)c.plan_stride);
   ALLOC(S.err, n);
   ALLOC(S.counters, 4);  // env steps, episodes, map-queue entries generated, overflow requests served
                          // (state blob: the first two)
@@ -5288,8 +5341,22 @@ int pgtg_create(const PgtgConfig* cfg, uint64_t n_envs, int32_t device, pgtg_han
     pgtg_destroy(h);
     return rc;
   }
+  // the tile plans: a row per env, or -- k_envq handles -- the cur slot of the env's map ring (plan_row)
+  const bool slot_plan = h->slot_plan = h->L.queue && h->q_block == 0;
+  if (slot_plan && n > (1ull << 30)) {  // (a refill request names env << 2 | slot in one word)
+    rc = fail(h, PGTG_E_UNSUPPORTED, "more than 2^30 envs with the persistent map-queue step kernel");
+    g_create_err = h->err;
+    pgtg_destroy(h);
+    return rc;
+  }
+  if (!slot_plan && (rc = dalloc(h, &h->S.plan, n * (uint64_t)c.plan_stride))) {
+    g_create_err = h->err;
+    pgtg_destroy(h);
+    return rc;
+  }
   if (h->L.queue) {
     if ((rc = dalloc(h, &h->S.qbuf, n * (uint64_t)queue_depth(h) * (uint64_t)c.qrec_dw)) || (rc = dalloc(h, &h->S.qstate, n)) ||
+        (slot_plan && (rc = hipMemset(h->S.qstate, 0x04, n) == hipSuccess ? 0 : fail(h, PGTG_E_DEVICE, "hipMemset failed"))) ||
         (!h->q_block &&
          ((rc = dalloc(h, &h->S.qreq, 2 * h->q_grid * queue_req_cap((n + h->L.envs - 1) / h->L.envs, h->q_grid, h->L.envs))) ||
           (rc = dalloc(h, &h->S.qovf, 2 * 8 * ((h->q_grid + 7) / 8) * (uint64_t)h->L.envs)) ||
@@ -5534,6 +5601,22 @@ static int read_traf(pgtg_handle* h, uint64_t env, uint4* t) {
   return 0;
 }
 
+// One env's tile plan (plan_stride u16 words; the host side of the kernels' plan_row): its row, or the
+// tile quads of the cur slot of its map ring.
+static int read_plan_row(pgtg_handle* h, uint64_t env, std::vector<uint16_t>& p) {
+  const DevCfg& c = h->hcfg;
+  p.assign((size_t)c.plan_stride, 0);
+  if (h->S.plan) {
+    HIPCHK(h, hipMemcpy(p.data(), h->S.plan + env * (uint64_t)c.plan_stride, p.size() * 2, hipMemcpyDeviceToHost));
+    return 0;
+  }
+  uint8_t qs = 0;
+  HIPCHK(h, hipMemcpy(&qs, h->S.qstate + env, 1, hipMemcpyDeviceToHost));
+  const uint32_t* slot = h->S.qbuf + (env * kQueueDepth + queue_cur(qs)) * (uint64_t)c.qrec_dw;
+  HIPCHK(h, hipMemcpy(p.data(), slot, std::min(p.size() * 2, (size_t)c.plan_dq * 16), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int pgtg_get_env_state(pgtg_handle* h, uint64_t env, PgtgEnvState* st) {
   if (!h || !st || env >= h->n) return PGTG_E_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
@@ -5558,8 +5641,8 @@ int pgtg_get_env_state(pgtg_handle* h, uint64_t env, PgtgEnvState* st) {
   st->spawn_counter = r.b.y;
   st->used_subgoals[0] = (uint64_t)r.b.z | ((uint64_t)r.b.w << 32);
   if (h->hcfg.nt > kSmallTiles) {  // maps of > 64 tiles mark the plan words (kPlanUsed)
-    std::vector<uint16_t> p(h->hcfg.plan_stride);
-    HIPCHK(h, hipMemcpy(p.data(), h->S.plan + env * (uint64_t)h->hcfg.plan_stride, p.size() * 2, hipMemcpyDeviceToHost));
+    std::vector<uint16_t> p;
+    if (int rc = read_plan_row(h, env, p)) return rc;
     st->used_subgoals[0] = 0;
     for (int t = 0; t < h->hcfg.nt; t++) st->used_subgoals[t >> 6] |= (uint64_t)((p[t] & kPlanUsed) != 0) << (t & 63);
   }
@@ -5652,9 +5735,9 @@ int pgtg_get_map_plan(pgtg_handle* h, uint64_t env, int32_t* w, int32_t* h_, uin
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   const DevCfg& c = h->hcfg;
-  std::vector<uint16_t> p(c.plan_stride);
+  std::vector<uint16_t> p;
   EnvRec r;
-  HIPCHK(h, hipMemcpy(p.data(), h->S.plan + env * (uint64_t)c.plan_stride, c.plan_stride * 2, hipMemcpyDeviceToHost));
+  if (int rc = read_plan_row(h, env, p)) return rc;
   HIPCHK(h, hipMemcpy(&r, h->S.rec + env, sizeof r, hipMemcpyDeviceToHost));
   *w = c.tw;
   *h_ = c.th;
@@ -5942,7 +6025,8 @@ static void snapshot_shape(pgtg_handle* h, PgtgStateHeader* hd, int* depth) {
   hd->qrec_dw = (uint32_t)h->hcfg.qrec_dw;
   hd->car_slots = (uint32_t)h->hcfg.car_slots;
   hd->cfg_hash = cfg_hash(h->hcfg);
-  *depth = h->S.qbuf ? queue_depth(h) : 0;
+  // (both step kernels' rings hold three maps; k_envq's keep the live plan in a slot: another layout)
+  *depth = h->S.qbuf ? (queue_depth(h) | (h->S.plan ? 0 : 0x100)) : 0;
 }
 
 static uint64_t section_bytes(const StateSection& s, uint64_t n) {
@@ -6010,7 +6094,7 @@ static int snapshot_table(pgtg_handle* h, const pgtg_snapshot* s, bool to_snapsh
     return fail(h, PGTG_E_INVALID, std::string(who) + ": the snapshot was created from a handle of another configuration");
   if (depth != s->depth)
     return fail(h, PGTG_E_INVALID, std::string(who) + ": the snapshot was created from a handle with another map-queue step "
-                                                      "kernel (its rings hold another number of maps)");
+                                                      "kernel (its map rings have another layout)");
   memset(T, 0, sizeof *T);
   uint32_t k = 0;
   for (const auto& hs : state_sections(h)) {
