@@ -4653,20 +4653,42 @@ struct pgtg_handle {
 };
 
 
+// Every step-kernel instance, once: its argument list (launch) and the name pgtg_step_kernel reports, alone
+// and with k_traffic behind it.  The SLOT instances of k_env (a k_envq handle: an env's plan is in its ring
+// slot) report as their counterparts with plan rows.  Two rows per family: BIG (maps of > 64 tiles), then not.
+enum StepArgs { ARGS_ENV, ARGS_ENVB, ARGS_ENVQ };
+enum StepFamily { ENV_TR_SLOT, ENV_SLOT, ENV_TR, ENVB, ENVQ, ENV, kStepFamilies };
+struct StepKernel {
+  const void* fn;
+  StepArgs args;
+  const char *name, *name_traffic;
+};
+#define STEP_ROW(fn, args, name) {(const void*)fn, args, name, name " + pgtg::k_traffic"}
+static const StepKernel kStepKernels[2 * kStepFamilies] = {
+    STEP_ROW((k_env<true, true, true>), ARGS_ENV, "pgtg::k_env<true, true>"),
+    STEP_ROW((k_env<true, false, true>), ARGS_ENV, "pgtg::k_env<true, false>"),
+    STEP_ROW((k_env<false, true, true>), ARGS_ENV, "pgtg::k_env<false, true>"),
+    STEP_ROW((k_env<false, false, true>), ARGS_ENV, "pgtg::k_env<false, false>"),
+    STEP_ROW((k_env<true, true>), ARGS_ENV, "pgtg::k_env<true, true>"),
+    STEP_ROW((k_env<true, false>), ARGS_ENV, "pgtg::k_env<true, false>"),
+    STEP_ROW((k_envb<true>), ARGS_ENVB, "pgtg::k_envb<true>"),
+    STEP_ROW((k_envb<false>), ARGS_ENVB, "pgtg::k_envb<false>"),
+    STEP_ROW((k_envq<true>), ARGS_ENVQ, "pgtg::k_envq<true>"),
+    STEP_ROW((k_envq<false>), ARGS_ENVQ, "pgtg::k_envq<false>"),
+    STEP_ROW((k_env<false, true>), ARGS_ENV, "pgtg::k_env<false, true>"),
+    STEP_ROW((k_env<false, false>), ARGS_ENV, "pgtg::k_env<false, false>"),
+};
+#undef STEP_ROW
+
 // The step kernel instance a launch of `mode` runs (traffic/rules: k_env<true>; random maps without
-// them: k_envq for steps when the map queue is on, else k_env<false>; BIG: maps of > 64 tiles).
-static const void* step_fn(const pgtg_handle* h, int mode) {
-  const bool big = h->hcfg.nt > kSmallTiles;
-  if (h->slot_plan) {  // a k_envq handle: the k_env instances that find an env's plan in its ring slot
-    if (h->hcfg.n_rules > 0) return big ? (const void*)k_env<true, true, true> : (const void*)k_env<true, false, true>;
-    if (mode != MODE_STEP || !h->L.queue) return big ? (const void*)k_env<false, true, true> : (const void*)k_env<false, false, true>;
-  }
-  if (h->hcfg.need_car || h->hcfg.n_rules > 0) return big ? (const void*)k_env<true, true> : (const void*)k_env<true, false>;
-  if (mode == MODE_STEP && h->L.queue) {
-    if (h->q_block == 1) return big ? (const void*)k_envb<true> : (const void*)k_envb<false>;
-    return big ? (const void*)k_envq<true> : (const void*)k_envq<false>;
-  }
-  return big ? (const void*)k_env<false, true> : (const void*)k_env<false, false>;
+// them: k_envq or k_envb for steps when the map queue is on, else k_env<false>).
+static const StepKernel& step_fn(const pgtg_handle* h, int mode) {
+  StepFamily f = ENV;
+  if (h->slot_plan && h->hcfg.n_rules > 0) f = ENV_TR_SLOT;  // (a k_envq handle keeps no plan rows)
+  else if (h->slot_plan && (mode != MODE_STEP || !h->L.queue)) f = ENV_SLOT;
+  else if (h->hcfg.need_car || h->hcfg.n_rules > 0) f = ENV_TR;
+  else if (mode == MODE_STEP && h->L.queue) f = h->q_block == 1 ? ENVB : ENVQ;
+  return kStepKernels[2 * f + (h->hcfg.nt > kSmallTiles ? 0 : 1)];
 }
 
 // slots per env ring of this handle's map queue (three in both kernels; k_envq's hold the live plan too: snapshot_shape)
@@ -4709,6 +4731,20 @@ static int dalloc(pgtg_handle* h, T** p, size_t count) {
 static int fail(pgtg_handle* h, int code, const std::string& m) {
   h->err = m;
   return code;
+}
+
+// the device's CU count (256, an MI355X's, where the query fails)
+static int cu_count(int device) {
+  int ncu = 0;
+  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ncu < 1) ncu = 256;
+  return ncu;
+}
+
+// before the host reads or writes device state: the handle's device current, its stream drained
+static int host_sync(pgtg_handle* h) {
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
 }
 
 // atan2 octant tables (host libm == CPython math.atan2) ---------------------------------------
@@ -5046,6 +5082,11 @@ static int derive_cfg(pgtg_handle* h, const PgtgConfig& in, DevCfg& c) {
   return 0;
 }
 
+static void set_sub_envs(Lds& l, int sub) {  // the observation image built for `sub` envs at a time
+  l.sub_envs = sub;
+  l.stream_words = img_words(sub, l.seg_bits);
+}
+
 extern "C" {
 
 // Launch shapes of a handle from its config and batch size: envs per workgroup, the LDS layout of
@@ -5077,10 +5118,7 @@ static int choose_launch(pgtg_handle* h, bool allow_queue) {
     // traffic: the most envs per workgroup (<= 128) for which two workgroups share a CU's LDS
     // after shrinking the observation sub-batch; else the largest that fits at all
     auto shrink = [&](Lds l) {
-      while (l.sub_envs > 8 && lds_bytes(l) + sizeof(Tables) > 80 * 1024) {
-        l.sub_envs /= 2;
-        l.stream_words = img_words(l.sub_envs, l.seg_bits);
-      }
+      while (l.sub_envs > 8 && lds_bytes(l) + sizeof(Tables) > 80 * 1024) set_sub_envs(l, l.sub_envs / 2);
       return l;
     };
     Lds best = shrink(lds_layout(c, envs));
@@ -5093,10 +5131,7 @@ static int choose_launch(pgtg_handle* h, bool allow_queue) {
     // (Two workgroups of two waves each land on three SIMDs, tools/micro/hwid2.hip.)
     if ((h->tune_epb == 0 && n_envs >= (uint64_t)256 * kBlock) || h->tune_epb == kBlock) {
       Lds l = lds_layout(c, kBlock);
-      while (l.sub_envs > 8 && lds_bytes(l) + sizeof(Tables) > 160 * 1024) {
-        l.sub_envs /= 2;
-        l.stream_words = img_words(l.sub_envs, l.seg_bits);
-      }
+      while (l.sub_envs > 8 && lds_bytes(l) + sizeof(Tables) > 160 * 1024) set_sub_envs(l, l.sub_envs / 2);
       if (lds_bytes(l) + sizeof(Tables) <= 160 * 1024) best = l;
     }
     h->L = best;
@@ -5107,17 +5142,10 @@ static int choose_launch(pgtg_handle* h, bool allow_queue) {
     const uint64_t blocks = (n_envs + kBlock - 1) / kBlock;
     const int want = (int)std::min<uint64_t>(4, (blocks + 255) / 256);
     auto fit = [&](const Lds& l) { return (int)((160 * 1024) / (lds_bytes(l) + sizeof(Tables))); };
-    while (fit(h->L) < want && h->L.sub_envs > 64) {
-      h->L.sub_envs /= 2;
-      h->L.stream_words = img_words(h->L.sub_envs, h->L.seg_bits);
-    }
+    while (fit(h->L) < want && h->L.sub_envs > 64) set_sub_envs(h->L, h->L.sub_envs / 2);
   }
-  if (h->tune_obs_sub >= 1 && h->tune_obs_sub < h->L.sub_envs) {  // forced observation sub-batch
-    h->L.sub_envs = h->tune_obs_sub;
-    h->L.stream_words = img_words(h->tune_obs_sub, h->L.seg_bits);
-  } else {
-    lds_img_in_traf(h->L, c);
-  }
+  if (h->tune_obs_sub >= 1 && h->tune_obs_sub < h->L.sub_envs) set_sub_envs(h->L, h->tune_obs_sub);  // forced
+  else lds_img_in_traf(h->L, c);
   if (c.need_car) {
     // k_traffic: per-lane plan + reset scratch
     h->kt_plan_dw = odd_up((c.nt + 1) / 2);
@@ -5135,9 +5163,7 @@ static int choose_launch(pgtg_handle* h, bool allow_queue) {
     }
     if (h->tune_kt_cap >= 1 && h->tune_kt_cap <= h->kt_cap) h->kt_cap = h->tune_kt_cap;
     h->kt_lds = 4 * h->kt_cap * per_env;
-    int ncu = 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || ncu < 1) ncu = 256;
-    h->kt_grid = (int)std::min<uint64_t>((uint64_t)ncu * wpc, (h->n + 3) / 4);
+    h->kt_grid = (int)std::min<uint64_t>((uint64_t)cu_count(h->device) * wpc, (h->n + 3) / 4);
     if (h->tune_kt_grid > 0) h->kt_grid = h->tune_kt_grid;  // forced grid: rounds, lane groups
     if (h->kt_lds + sizeof(Tables) > 160 * 1024) return fail(h, PGTG_E_UNSUPPORTED, "LDS budget exceeded (traffic reset scratch)");
     if (h->kt_lds > 64 * 1024)
@@ -5153,20 +5179,15 @@ static int choose_launch(pgtg_handle* h, bool allow_queue) {
   h->lds = lds_bytes(h->L);
   if (h->lds + sizeof(Tables) > 160 * 1024) return fail(h, PGTG_E_UNSUPPORTED, "LDS budget exceeded");
   if (h->lds > 64 * 1024) {
-    const void* fns[] = {(const void*)k_env<true, false>, (const void*)k_env<false, false>, (const void*)k_envq<false>,
-                         (const void*)k_env<true, true>, (const void*)k_env<false, true>, (const void*)k_envq<true>,
-                         (const void*)k_envb<false>, (const void*)k_envb<true>,
-                         (const void*)k_env<true, false, true>, (const void*)k_env<false, false, true>,
-                         (const void*)k_env<true, true, true>, (const void*)k_env<false, true, true>};
-    for (const void* f : fns) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds);
+    for (const StepKernel& k : kStepKernels)
+      (void)hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds);
   }
   // first-round start offsets (stagger_start) for the launches without traffic
   if (!c.need_car && c.n_rules == 0) {
-    int ncu = 0, per_cu = 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || ncu < 1) ncu = 256;
-    const void* fn = step_fn(h, MODE_STEP);
+    int per_cu = 0;
+    const void* fn = step_fn(h, MODE_STEP).fn;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, h->lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    h->L.stagger_wgs = ncu * per_cu;
+    h->L.stagger_wgs = cu_count(h->device) * per_cu;
     // only launches of two rounds or more: one round has no later workgroups to keep the offsets
     // (1 048 576 5x5 envs, 8 rounds: k_envq 476 -> 460 us; 262 144 envs, 2 rounds: 140 -> 133 us;
     // one round: 66 -> 78 us, profiles/r03/abrec/stagger_by_shard.txt)
@@ -5188,82 +5209,56 @@ static int choose_launch(pgtg_handle* h, bool allow_queue) {
   return PGTG_OK;
 }
 
-int pgtg_create(const PgtgConfig* cfg, uint64_t n_envs, int32_t device, pgtg_handle** out) {
-  if (!cfg || !out) return PGTG_E_INVALID;
-  pgtg_handle* h = new pgtg_handle();
-  *out = nullptr;
-  h->device = device;
-  h->n = n_envs;
+// pgtg_create on a fresh handle that knows its device and batch size: a code and h->err on failure, whatever
+// was allocated until then left in h->allocs for pgtg_destroy.
+static int create(pgtg_handle* h, const PgtgConfig* cfg) {
   h->tune_epb = cfg->tune_envs_per_block;
   h->tune_obs_sub = cfg->tune_obs_sub;
   h->tune_kt_grid = cfg->tune_kt_grid;
   h->tune_kt_cap = cfg->tune_kt_cap;
   h->tune_kt_wpc = cfg->tune_kt_wpc;
   h->tune_queue_mode = cfg->tune_queue_mode;
-  int rc = 0;
-  if (n_envs == 0) rc = fail(h, PGTG_E_INVALID, "n_envs must be > 0");
-  if (!rc) rc = derive_cfg(h, *cfg, h->hcfg);
-  if (rc) {
-    g_create_err = h->err;
-    delete h;
-    return rc;
-  }
-  if (hipSetDevice(device) != hipSuccess) {
-    g_create_err = "hipSetDevice failed";
-    delete h;
-    return PGTG_E_DEVICE;
-  }
+  if (h->n == 0) return fail(h, PGTG_E_INVALID, "n_envs must be > 0");
+  if (int rc = derive_cfg(h, *cfg, h->hcfg)) return rc;
+  if (hipSetDevice(h->device) != hipSuccess) return fail(h, PGTG_E_DEVICE, "hipSetDevice failed");
   const DevCfg& c = h->hcfg;
   DevState& S = h->S;
-  S.n = n_envs;
-  uint64_t n = n_envs;
-#define ALLOC(p, cnt)                 \
-  if ((rc = dalloc(h, &(p), (cnt)))) { \
-    g_create_err = h->err;            \
-    pgtg_destroy(h);                  \
-    return rc;                        \
-  }
-  ALLOC(h->dcfg, 1);
-  ALLOC(S.rec, n);
-  ALLOC(S.seed, n);
-  ALLOC(S.err, n);
-  ALLOC(S.counters, 4);  // env steps, episodes, map-queue entries generated, overflow requests served
-                         // (state blob: the first two)
-  ALLOC(S.wg_ticks, 1);
+  const uint64_t n = S.n = h->n;
+  if (int rc = dalloc(h, &h->dcfg, 1)) return rc;
+  if (int rc = dalloc(h, &S.rec, n)) return rc;
+  if (int rc = dalloc(h, &S.seed, n)) return rc;
+  if (int rc = dalloc(h, &S.err, n)) return rc;
+  // env steps, episodes, map-queue entries generated, overflow requests served (state blob: the first two)
+  if (int rc = dalloc(h, &S.counters, 4)) return rc;
+  if (int rc = dalloc(h, &S.wg_ticks, 1)) return rc;
   DevStream* streams[4] = {&S.car, &S.ice, &S.broken, &S.sand};
   int needs[4] = {c.need_car, c.need_ice, c.need_broken, c.need_sand};
   for (int k = 0; k < 4; k++)
-    if (needs[k]) {
-      ALLOC(streams[k]->shi, n);
-      ALLOC(streams[k]->slo, n);
-      ALLOC(streams[k]->ihi, n);
-      ALLOC(streams[k]->ilo, n);
-      ALLOC(streams[k]->buf, n);
-    }
-  if (c.visited_penalty != 0.0) ALLOC(S.visited, n * (uint64_t)c.vis_words);
+    if (needs[k])
+      for (uint64_t** p : {&streams[k]->shi, &streams[k]->slo, &streams[k]->ihi, &streams[k]->ilo, &streams[k]->buf})
+        if (int rc = dalloc(h, p, n)) return rc;
+  if (c.visited_penalty != 0.0)
+    if (int rc = dalloc(h, &S.visited, n * (uint64_t)c.vis_words)) return rc;
   if (c.nt > kSmallTiles) {  // maps of > 64 tiles read their edge table from global memory
     uint32_t* e = nullptr;
-    ALLOC(e, h->epk.size());
-    if (hipMemcpy(e, h->epk.data(), h->epk.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-      g_create_err = "edge table upload failed";
-      pgtg_destroy(h);
-      return PGTG_E_DEVICE;
-    }
+    if (int rc = dalloc(h, &e, h->epk.size())) return rc;
+    if (hipMemcpy(e, h->epk.data(), h->epk.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
+      return fail(h, PGTG_E_DEVICE, "edge table upload failed");
     S.epk = e;
   }
   if (c.need_car) {
-    ALLOC(S.car_w0, (uint64_t)c.car_slots * n);
-    ALLOC(S.car_w1, (uint64_t)c.car_slots * n);
     S.sp_pitch = (uint32_t)((c.max_spawners + 7) & ~7);
     S.fresh_occ = (uint32_t)((c.car_cap + 3) & ~3);
     S.fresh_dw = S.fresh_occ + (uint32_t)c.nt * 4u;
-    ALLOC(S.car_id, (uint64_t)c.car_slots * n);
-    ALLOC(S.traf, n);
-    ALLOC(S.occ, (uint64_t)c.nt * 4 * n);
-    ALLOC(S.fresh, (uint64_t)S.fresh_dw * n);
-    ALLOC(S.spawners, (uint64_t)S.sp_pitch * n);
-    ALLOC(S.tr_list, n);
-    ALLOC(S.tr_count, 2);
+    if (int rc = dalloc(h, &S.car_w0, (uint64_t)c.car_slots * n)) return rc;
+    if (int rc = dalloc(h, &S.car_w1, (uint64_t)c.car_slots * n)) return rc;
+    if (int rc = dalloc(h, &S.car_id, (uint64_t)c.car_slots * n)) return rc;
+    if (int rc = dalloc(h, &S.traf, n)) return rc;
+    if (int rc = dalloc(h, &S.occ, (uint64_t)c.nt * 4 * n)) return rc;
+    if (int rc = dalloc(h, &S.fresh, (uint64_t)S.fresh_dw * n)) return rc;
+    if (int rc = dalloc(h, &S.spawners, (uint64_t)S.sp_pitch * n)) return rc;
+    if (int rc = dalloc(h, &S.tr_list, n)) return rc;
+    if (int rc = dalloc(h, &S.tr_count, 2)) return rc;
   }
   // atan2 tables
   {
@@ -5274,18 +5269,14 @@ int pgtg_create(const PgtgConfig* cfg, uint64_t n_envs, int32_t device, pgtg_han
       for (int b = 0; b < c.cmp_pitch; b++)
         cmp[(size_t)a * c.cmp_pitch + b] = compass_dir(a - c.cmp_off, b - c.cmp_off, cfg->sliding_size);
     int8_t *dn = nullptr, *dc = nullptr;
-    ALLOC(dn, nsd.size());
-    ALLOC(dc, cmp.size());
+    if (int rc = dalloc(h, &dn, nsd.size())) return rc;
+    if (int rc = dalloc(h, &dc, cmp.size())) return rc;
     if (hipMemcpy(dn, nsd.data(), nsd.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dc, cmp.data(), cmp.size(), hipMemcpyHostToDevice) != hipSuccess) {
-      g_create_err = "table upload failed";
-      pgtg_destroy(h);
-      return PGTG_E_DEVICE;
-    }
+        hipMemcpy(dc, cmp.data(), cmp.size(), hipMemcpyHostToDevice) != hipSuccess)
+      return fail(h, PGTG_E_DEVICE, "table upload failed");
     S.nsd_tab = dn;
     S.cmp_tab = dc;
   }
-#undef ALLOC
   {
     Tables t;
     memset(&t, 0, sizeof t);
@@ -5325,46 +5316,42 @@ int pgtg_create(const PgtgConfig* cfg, uint64_t n_envs, int32_t device, pgtg_han
     memcpy(t.beh_t, h->hcfg.beh_t, sizeof t.beh_t);
     memcpy(t.beh_mf, h->hcfg.beh_min_follow, sizeof t.beh_mf);
     memcpy(t.beh_pt, h->hcfg.beh_patience_thr, sizeof t.beh_pt);
-    if ((rc = dalloc(h, &h->dtab, 1)) || hipMemcpy(h->dtab, &t, sizeof t, hipMemcpyHostToDevice) != hipSuccess) {
-      g_create_err = "table upload failed";
-      pgtg_destroy(h);
-      return PGTG_E_DEVICE;
-    }
+    if (dalloc(h, &h->dtab, 1) || hipMemcpy(h->dtab, &t, sizeof t, hipMemcpyHostToDevice) != hipSuccess)
+      return fail(h, PGTG_E_DEVICE, "table upload failed");
   }
-  if (hipMemcpy(h->dcfg, &h->hcfg, sizeof(DevCfg), hipMemcpyHostToDevice) != hipSuccess) {
-    g_create_err = "config upload failed";
-    pgtg_destroy(h);
-    return PGTG_E_DEVICE;
-  }
-  if ((rc = choose_launch(h, true))) {
-    g_create_err = h->err;
-    pgtg_destroy(h);
-    return rc;
-  }
+  if (hipMemcpy(h->dcfg, &h->hcfg, sizeof(DevCfg), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(h, PGTG_E_DEVICE, "config upload failed");
+  if (int rc = choose_launch(h, true)) return rc;
   // the tile plans: a row per env, or -- k_envq handles -- the cur slot of the env's map ring (plan_row)
-  const bool slot_plan = h->slot_plan = h->L.queue && h->q_block == 0;
-  if (slot_plan && n > (1ull << 30)) {  // (a refill request names env << 2 | slot in one word)
-    rc = fail(h, PGTG_E_UNSUPPORTED, "more than 2^30 envs with the persistent map-queue step kernel");
-    g_create_err = h->err;
-    pgtg_destroy(h);
-    return rc;
-  }
-  if (!slot_plan && (rc = dalloc(h, &h->S.plan, n * (uint64_t)c.plan_stride))) {
-    g_create_err = h->err;
-    pgtg_destroy(h);
-    return rc;
-  }
+  h->slot_plan = h->L.queue && h->q_block == 0;
+  if (h->slot_plan && n > (1ull << 30))  // (a refill request names env << 2 | slot in one word)
+    return fail(h, PGTG_E_UNSUPPORTED, "more than 2^30 envs with the persistent map-queue step kernel");
+  if (!h->slot_plan)
+    if (int rc = dalloc(h, &S.plan, n * (uint64_t)c.plan_stride)) return rc;
   if (h->L.queue) {
-    if ((rc = dalloc(h, &h->S.qbuf, n * (uint64_t)queue_depth(h) * (uint64_t)c.qrec_dw)) || (rc = dalloc(h, &h->S.qstate, n)) ||
-        (slot_plan && (rc = hipMemset(h->S.qstate, 0x04, n) == hipSuccess ? 0 : fail(h, PGTG_E_DEVICE, "hipMemset failed"))) ||
-        (!h->q_block &&
-         ((rc = dalloc(h, &h->S.qreq, 2 * h->q_grid * queue_req_cap((n + h->L.envs - 1) / h->L.envs, h->q_grid, h->L.envs))) ||
-          (rc = dalloc(h, &h->S.qovf, 2 * 8 * ((h->q_grid + 7) / 8) * (uint64_t)h->L.envs)) ||
-          (rc = dalloc(h, &h->S.qctr, kQctrWords))))) {
-      g_create_err = h->err;
-      pgtg_destroy(h);
-      return rc;
-    }
+    if (int rc = dalloc(h, &S.qbuf, n * (uint64_t)queue_depth(h) * (uint64_t)c.qrec_dw)) return rc;
+    if (int rc = dalloc(h, &S.qstate, n)) return rc;
+    if (h->slot_plan && hipMemset(S.qstate, 0x04, n) != hipSuccess) return fail(h, PGTG_E_DEVICE, "hipMemset failed");
+  }
+  if (h->L.queue && !h->q_block) {  // k_envq's request lists, overflow lists and counters
+    const uint64_t blocks = (n + h->L.envs - 1) / h->L.envs;
+    if (int rc = dalloc(h, &S.qreq, 2 * h->q_grid * queue_req_cap(blocks, h->q_grid, h->L.envs))) return rc;
+    if (int rc = dalloc(h, &S.qovf, 2 * 8 * ((h->q_grid + 7) / 8) * (uint64_t)h->L.envs)) return rc;
+    if (int rc = dalloc(h, &S.qctr, kQctrWords)) return rc;
+  }
+  return PGTG_OK;
+}
+
+int pgtg_create(const PgtgConfig* cfg, uint64_t n_envs, int32_t device, pgtg_handle** out) {
+  if (!cfg || !out) return PGTG_E_INVALID;
+  *out = nullptr;
+  pgtg_handle* h = new pgtg_handle();
+  h->device = device;
+  h->n = n_envs;
+  if (int rc = create(h, cfg)) {
+    g_create_err = h->err;
+    pgtg_destroy(h);
+    return rc;
   }
   *out = h;
   return PGTG_OK;
@@ -5444,25 +5431,17 @@ static int launch_flatten(pgtg_handle* h, int mode, uint64_t grid) {
                                  : (pair ? (const void*)k_flatten<float, true, 2>
                                          : (one ? (const void*)k_flatten<float, true, 1> : (const void*)k_flatten<float, false, 1>));
   if (h->flat_fn != fn) {  // the workgroups resident at once (kernel registers), fixed per variant
-    int ncu = 0, per_cu = 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || ncu < 1) ncu = 256;
+    int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
     h->flat_fn = fn;
-    h->flat_wgs = (uint64_t)ncu * (uint64_t)per_cu;
+    h->flat_wgs = (uint64_t)cu_count(h->device) * (uint64_t)per_cu;
   }
   // rows per workgroup <= 256; one round of resident workgroups where the batch allows.  (The grid
   // hardly matters: 256 / 512 / 1 536 / 3 072 workgroups 150 / 138 / 139 / 134 us per step at 65 536
   // envs, profiles/r06/flat_grid_sweep.txt -- the kernel is bound chip-wide, not by waves in flight)
   const uint64_t G = grid ? grid : std::max<uint64_t>(std::min<uint64_t>(h->n, h->flat_wgs), (h->n + 255) / 256);
-  if (h->flat_dtype) {
-    if (one) hipLaunchKernelGGL((k_flatten<int8_t, true, 1>), dim3((unsigned)G), dim3(256), 0, h->stream, a);
-    else hipLaunchKernelGGL((k_flatten<int8_t, false, 1>), dim3((unsigned)G), dim3(256), 0, h->stream, a);
-  } else if (pair) {
-    hipLaunchKernelGGL((k_flatten<float, true, 2>), dim3((unsigned)G), dim3(256), 0, h->stream, a);
-  } else {
-    if (one) hipLaunchKernelGGL((k_flatten<float, true, 1>), dim3((unsigned)G), dim3(256), 0, h->stream, a);
-    else hipLaunchKernelGGL((k_flatten<float, false, 1>), dim3((unsigned)G), dim3(256), 0, h->stream, a);
-  }
+  void* args[] = {&a};
+  HIPCHK(h, hipLaunchKernel(fn, dim3((unsigned)G), dim3(256), args, 0, h->stream));
   HIPCHK(h, hipGetLastError());
   return PGTG_OK;
 }
@@ -5482,19 +5461,22 @@ static int launch(pgtg_handle* h, const uint8_t* actions, const uint8_t* mask, i
     }
     HIPCHK(h, hipEventRecord(h->evpool[h->ev_used], h->stream));
   }
-  const void* fn = step_fn(h, mode);
+  const StepKernel& k = step_fn(h, mode);
+  uint32_t qsel = (uint32_t)(h->q_launch % 3) | (uint32_t)(h->q_launch & 1) << 2;  // k_envq: its rotating lists
   void* args[] = {&h->dcfg, &h->dtab, &h->S, &actions, &mask, &h->out, &mode, &h->L, &h->tr_slot};
-  if (fn == (const void*)k_envb<false> || fn == (const void*)k_envb<true>) {
-    void* bargs[] = {&h->dcfg, &h->dtab, &h->S, &actions, &h->out, &h->L};
-    HIPCHK(h, hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(kBlock), bargs, h->lds, h->stream));
-  } else if (fn == (const void*)k_envq<false> || fn == (const void*)k_envq<true>) {
-    uint32_t qsel = (uint32_t)(h->q_launch % 3) | (uint32_t)(h->q_launch & 1) << 2;
-    h->q_launch++;
-    void* qargs[] = {&h->dcfg, &h->dtab, &h->S, &actions, &h->out, &h->L, &qsel};
-    HIPCHK(h, hipLaunchKernel(fn, dim3((unsigned)std::min(blocks, h->q_grid)), dim3(kBlock), qargs, h->lds, h->stream));
-  } else {
-    HIPCHK(h, hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(kBlock), args, h->lds, h->stream));
+  void* bargs[] = {&h->dcfg, &h->dtab, &h->S, &actions, &h->out, &h->L};
+  void* qargs[] = {&h->dcfg, &h->dtab, &h->S, &actions, &h->out, &h->L, &qsel};
+  void** kargs = args;
+  switch (k.args) {
+    case ARGS_ENV: break;
+    case ARGS_ENVB: kargs = bargs; break;
+    case ARGS_ENVQ:  // the persistent grid
+      kargs = qargs;
+      h->q_launch++;
+      blocks = std::min(blocks, h->q_grid);
+      break;
   }
+  HIPCHK(h, hipLaunchKernel(k.fn, dim3((unsigned)blocks), dim3(kBlock), kargs, h->lds, h->stream));
   HIPCHK(h, hipGetLastError());
   if (h->hcfg.need_car && mode != MODE_OBSERVE) {
     // initial traffic of the envs reset by this launch; it also sets their new cars' squares in the
@@ -5619,8 +5601,7 @@ static int read_plan_row(pgtg_handle* h, uint64_t env, std::vector<uint16_t>& p)
 
 int pgtg_get_env_state(pgtg_handle* h, uint64_t env, PgtgEnvState* st) {
   if (!h || !st || env >= h->n) return PGTG_E_INVALID;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (int rc = host_sync(h)) return rc;
   EnvRec r;
   uint64_t seed;
   uint8_t e;
@@ -5716,8 +5697,7 @@ int pgtg_get_cars(pgtg_handle* h, uint64_t env, PgtgCar* cars, int32_t cap, int3
   if (!h || env >= h->n || !n) return PGTG_E_INVALID;
   *n = 0;
   if (!h->hcfg.need_car) return PGTG_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (int rc = host_sync(h)) return rc;
   uint4 t;
   if (int rc = read_traf(h, env, &t)) return rc;
   *n = (int)(t.x & 0xffffu);
@@ -5732,8 +5712,7 @@ int pgtg_get_cars(pgtg_handle* h, uint64_t env, PgtgCar* cars, int32_t cap, int3
 int pgtg_get_map_plan(pgtg_handle* h, uint64_t env, int32_t* w, int32_t* h_, uint8_t* exits, int8_t* otype,
                       int8_t* omask, int32_t* start3, int32_t* goal3) {
   if (!h || env >= h->n) return PGTG_E_INVALID;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (int rc = host_sync(h)) return rc;
   const DevCfg& c = h->hcfg;
   std::vector<uint16_t> p;
   EnvRec r;
@@ -5779,8 +5758,7 @@ int pgtg_get_squares(pgtg_handle* h, uint64_t env, uint64_t* words, int32_t cap,
 int pgtg_set_rules(pgtg_handle* h, const PgtgRule* rules, int32_t n_rules) {
   if (!h || n_rules < 0 || n_rules > PGTG_MAX_RULES || (n_rules > 0 && !rules))
     return h ? fail(h, PGTG_E_INVALID, "bad rule count") : PGTG_E_INVALID;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (int rc = host_sync(h)) return rc;
   DevCfg& c = h->hcfg;
   const DevCfg old_cfg = c;
   const Lds old_L = h->L;
@@ -5812,8 +5790,7 @@ int pgtg_set_rules(pgtg_handle* h, const PgtgRule* rules, int32_t n_rules) {
 
 int pgtg_set_agent(pgtg_handle* h, uint64_t env, int32_t x, int32_t y, int32_t vx, int32_t vy) {
   if (!h || env >= h->n) return PGTG_E_INVALID;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (int rc = host_sync(h)) return rc;
   EnvRec r;
   HIPCHK(h, hipMemcpy(&r, h->S.rec + env, sizeof r, hipMemcpyDeviceToHost));
   r.a.x = ((uint32_t)x & 0xffffu) | ((uint32_t)y << 16);
@@ -5822,13 +5799,16 @@ int pgtg_set_agent(pgtg_handle* h, uint64_t env, int32_t x, int32_t y, int32_t v
   return PGTG_OK;
 }
 
+// a car the host may place: on the map, one of the 20 routes and 5 driver profiles
+static bool car_ok(const DevCfg& c, int x, int y, int route, int profile) {
+  return x >= 0 && y >= 0 && x < c.W && y < c.H && route >= 0 && route < 20 && profile >= 0 && profile < 5;
+}
+
 int pgtg_add_car(pgtg_handle* h, uint64_t env, int32_t x, int32_t y, int32_t route, int32_t profile, int32_t car_id) {
   if (!h || env >= h->n) return PGTG_E_INVALID;
   if (!h->hcfg.need_car) return fail(h, PGTG_E_UNSUPPORTED, "create the handle with min_car_capacity > 0 or traffic");
-  if (x < 0 || y < 0 || x >= h->hcfg.W || y >= h->hcfg.H || route < 0 || route >= 20 || profile < 0 || profile >= 5)
-    return fail(h, PGTG_E_INVALID, "car outside the map or bad route/profile");
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (!car_ok(h->hcfg, x, y, route, profile)) return fail(h, PGTG_E_INVALID, "car outside the map or bad route/profile");
+  if (int rc = host_sync(h)) return rc;
   uint4 t;
   if (int rc = read_traf(h, env, &t)) return rc;
   std::vector<PgtgCar> v;
@@ -5875,6 +5855,27 @@ uint64_t cfg_hash(const DevCfg& c) {  // DevCfg is zero-initialised (derive_cfg)
   return h;
 }
 }  // namespace
+
+// The shape record of a handle -- the header fields nt .. car_slots and cfg_hash -- for the blob and for
+// snapshots: what two handles must share to exchange state.
+static void shape_of(const pgtg_handle* h, PgtgStateHeader* hd) {
+  const DevCfg& c = h->hcfg;
+  hd->nt = (uint32_t)c.nt;
+  hd->car_cap = (uint32_t)c.car_cap;
+  hd->plan_stride = (uint32_t)c.plan_stride;
+  hd->max_spawners = (uint32_t)c.max_spawners;
+  hd->vis_words = (uint32_t)c.vis_words;
+  hd->qrec_dw = (uint32_t)c.qrec_dw;
+  hd->car_slots = (uint32_t)c.car_slots;
+  hd->cfg_hash = cfg_hash(c);
+}
+// nullptr when two shape records agree, else what the other handle is: "another shape" before "another configuration"
+static const char* shape_differs(const PgtgStateHeader& a, const PgtgStateHeader& b) {
+  if (a.nt != b.nt || a.car_cap != b.car_cap || a.plan_stride != b.plan_stride || a.max_spawners != b.max_spawners ||
+      a.vis_words != b.vis_words || a.qrec_dw != b.qrec_dw || a.car_slots != b.car_slots)
+    return "another shape";
+  return a.cfg_hash != b.cfg_hash ? "another configuration" : nullptr;
+}
 
 static std::vector<StateSection> state_sections(pgtg_handle* h) {
   const DevCfg& c = h->hcfg;
@@ -5940,14 +5941,7 @@ int pgtg_dump_state(pgtg_handle* h, void* buf, uint64_t bytes) {
   hd.version = kStateVersion;
   hd.n = h->n;
   hd.n_sections = (uint32_t)v.size();
-  hd.nt = (uint32_t)h->hcfg.nt;
-  hd.car_cap = (uint32_t)h->hcfg.car_cap;
-  hd.plan_stride = (uint32_t)h->hcfg.plan_stride;
-  hd.max_spawners = (uint32_t)h->hcfg.max_spawners;
-  hd.vis_words = (uint32_t)h->hcfg.vis_words;
-  hd.qrec_dw = (uint32_t)h->hcfg.qrec_dw;
-  hd.car_slots = (uint32_t)h->hcfg.car_slots;
-  hd.cfg_hash = cfg_hash(h->hcfg);
+  shape_of(h, &hd);
   memcpy(p, &hd, sizeof hd);
   uint64_t off = sizeof hd;
   for (const auto& s : v) {
@@ -5972,14 +5966,11 @@ int pgtg_load_state(pgtg_handle* h, const void* buf, uint64_t bytes) {
   memcpy(&hd, p, sizeof hd);
   if (memcmp(hd.magic, "PGTS", 4) != 0 || hd.version != kStateVersion)
     return fail(h, PGTG_E_INVALID, "pgtg_load_state: not a state blob of this version");
-  if (hd.n != h->n || hd.n_sections != v.size() || hd.nt != (uint32_t)h->hcfg.nt ||
-      hd.car_cap != (uint32_t)h->hcfg.car_cap || hd.plan_stride != (uint32_t)h->hcfg.plan_stride ||
-      hd.max_spawners != (uint32_t)h->hcfg.max_spawners || hd.vis_words != (uint32_t)h->hcfg.vis_words ||
-      hd.qrec_dw != (uint32_t)h->hcfg.qrec_dw || hd.car_slots != (uint32_t)h->hcfg.car_slots ||
-      bytes < state_blob_bytes(v))
-    return fail(h, PGTG_E_INVALID, "pgtg_load_state: the state was dumped from a handle of another shape");
-  if (hd.cfg_hash != cfg_hash(h->hcfg))
-    return fail(h, PGTG_E_INVALID, "pgtg_load_state: the state was dumped from a handle of another configuration");
+  PgtgStateHeader mine{};
+  shape_of(h, &mine);
+  const bool sized = hd.n == h->n && hd.n_sections == v.size() && bytes >= state_blob_bytes(v);  // (shape too)
+  if (const char* other = sized ? shape_differs(hd, mine) : "another shape")
+    return fail(h, PGTG_E_INVALID, std::string("pgtg_load_state: the state was dumped from a handle of ") + other);
   uint64_t off = sizeof hd;
   for (const auto& s : v) {
     PgtgSectionEntry e;
@@ -5987,8 +5978,7 @@ int pgtg_load_state(pgtg_handle* h, const void* buf, uint64_t bytes) {
     off += sizeof e;
     if (e.id != s.id || e.bytes != s.bytes) return fail(h, PGTG_E_INVALID, "pgtg_load_state: section table mismatch");
   }
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (int rc = host_sync(h)) return rc;
   for (const auto& s : v) {
     off = (off + 15) & ~15ull;
     HIPCHK(h, hipMemcpy(s.ptr, p + off, s.bytes, hipMemcpyHostToDevice));
@@ -6017,14 +6007,7 @@ struct pgtg_snapshot {
 };
 
 static void snapshot_shape(pgtg_handle* h, PgtgStateHeader* hd, int* depth) {
-  hd->nt = (uint32_t)h->hcfg.nt;
-  hd->car_cap = (uint32_t)h->hcfg.car_cap;
-  hd->plan_stride = (uint32_t)h->hcfg.plan_stride;
-  hd->max_spawners = (uint32_t)h->hcfg.max_spawners;
-  hd->vis_words = (uint32_t)h->hcfg.vis_words;
-  hd->qrec_dw = (uint32_t)h->hcfg.qrec_dw;
-  hd->car_slots = (uint32_t)h->hcfg.car_slots;
-  hd->cfg_hash = cfg_hash(h->hcfg);
+  shape_of(h, hd);
   // (both step kernels' rings hold three maps; k_envq's keep the live plan in a slot: another layout)
   *depth = h->S.qbuf ? (queue_depth(h) | (h->S.plan ? 0 : 0x100)) : 0;
 }
@@ -6085,13 +6068,9 @@ static int snapshot_table(pgtg_handle* h, const pgtg_snapshot* s, bool to_snapsh
   PgtgStateHeader hd{};
   int depth = 0;
   snapshot_shape(h, &hd, &depth);
-  const PgtgStateHeader& q = s->shape;
   if (h->device != s->device) return fail(h, PGTG_E_INVALID, std::string(who) + ": the snapshot lives on another device");
-  if (hd.nt != q.nt || hd.car_cap != q.car_cap || hd.plan_stride != q.plan_stride || hd.max_spawners != q.max_spawners ||
-      hd.vis_words != q.vis_words || hd.qrec_dw != q.qrec_dw || hd.car_slots != q.car_slots)
-    return fail(h, PGTG_E_INVALID, std::string(who) + ": the snapshot was created from a handle of another shape");
-  if (hd.cfg_hash != q.cfg_hash)
-    return fail(h, PGTG_E_INVALID, std::string(who) + ": the snapshot was created from a handle of another configuration");
+  if (const char* other = shape_differs(hd, s->shape))
+    return fail(h, PGTG_E_INVALID, std::string(who) + ": the snapshot was created from a handle of " + other);
   if (depth != s->depth)
     return fail(h, PGTG_E_INVALID, std::string(who) + ": the snapshot was created from a handle with another map-queue step "
                                                       "kernel (its map rings have another layout)");
@@ -6169,13 +6148,10 @@ int pgtg_set_to_state(pgtg_handle* h, uint64_t env, int32_t x, int32_t y, int32_
   const DevCfg& c = h->hcfg;
   if (n_cars > 0 && !c.need_car) return fail(h, PGTG_E_UNSUPPORTED, "create the handle with min_car_capacity > 0 or traffic");
   if (n_cars > c.car_cap) return fail(h, PGTG_E_UNSUPPORTED, "more cars than the handle's car capacity");
-  for (int k = 0; k < n_cars; k++) {
-    const PgtgCar& q = cars[k];
-    if (q.x < 0 || q.y < 0 || q.x >= c.W || q.y >= c.H || q.route < 0 || q.route >= 20 || q.profile < 0 || q.profile >= 5)
+  for (int k = 0; k < n_cars; k++)
+    if (!car_ok(c, cars[k].x, cars[k].y, cars[k].route, cars[k].profile))
       return fail(h, PGTG_E_INVALID, "car outside the map or bad route/profile");
-  }
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (int rc = host_sync(h)) return rc;
   EnvRec r;
   HIPCHK(h, hipMemcpy(&r, h->S.rec + env, sizeof r, hipMemcpyDeviceToHost));
   r.a.x = ((uint32_t)x & 0xffffu) | ((uint32_t)y << 16);
@@ -6203,12 +6179,18 @@ int pgtg_car_digest(pgtg_handle* h, uint64_t* out_dev) {
   return PGTG_OK;
 }
 
+// DevState::counters once the stream has drained: env steps, episodes, map-queue entries generated, overflow
+// requests served
+static int read_counters(pgtg_handle* h, unsigned long long (&c)[4]) {
+  if (int rc = host_sync(h)) return rc;
+  HIPCHK(h, hipMemcpy(c, h->S.counters, sizeof c, hipMemcpyDeviceToHost));
+  return PGTG_OK;
+}
+
 int pgtg_get_counters(pgtg_handle* h, uint64_t* env_steps, uint64_t* episodes) {
   if (!h) return PGTG_E_INVALID;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  unsigned long long c[2];
-  HIPCHK(h, hipMemcpy(c, h->S.counters, sizeof c, hipMemcpyDeviceToHost));
+  unsigned long long c[4];
+  if (int rc = read_counters(h, c)) return rc;
   if (env_steps) *env_steps = c[0];
   if (episodes) *episodes = c[1];
   return PGTG_OK;
@@ -6216,11 +6198,17 @@ int pgtg_get_counters(pgtg_handle* h, uint64_t* env_steps, uint64_t* episodes) {
 
 int pgtg_get_queue_maps(pgtg_handle* h, uint64_t* maps) {
   if (!h || !maps) return PGTG_E_INVALID;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  unsigned long long c[3];
-  HIPCHK(h, hipMemcpy(c, h->S.counters, sizeof c, hipMemcpyDeviceToHost));
+  unsigned long long c[4];
+  if (int rc = read_counters(h, c)) return rc;
   *maps = c[2];
+  return PGTG_OK;
+}
+
+int pgtg_get_queue_overflow(pgtg_handle* h, uint64_t* served) {
+  if (!h || !served) return PGTG_E_INVALID;
+  unsigned long long c[4];
+  if (int rc = read_counters(h, c)) return rc;
+  *served = c[3];
   return PGTG_OK;
 }
 
@@ -6317,8 +6305,7 @@ int pgtg_set_episode_stats(pgtg_handle* h, float* ep_return_dev, int32_t* ep_len
 int pgtg_episode_summary(pgtg_handle* h, PgtgEpisodeSummary* out, int32_t reset) {
   if (!h || !out) return PGTG_E_INVALID;
   if (!h->ep.rows) return fail(h, PGTG_E_INVALID, "pgtg_episode_summary: episode statistics were never bound");
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (int rc = host_sync(h)) return rc;
   std::vector<PgtgEpisodeSummary> rows(h->ep_rows);
   HIPCHK(h, hipMemcpy(rows.data(), h->ep.rows, rows.size() * sizeof(PgtgEpisodeSummary), hipMemcpyDeviceToHost));
   PgtgEpisodeSummary s{};
@@ -6445,20 +6432,9 @@ int pgtg_policy(pgtg_handle* h, const PgtgPolicy* a) {
   return PGTG_OK;
 }
 
-int pgtg_get_queue_overflow(pgtg_handle* h, uint64_t* served) {
-  if (!h || !served) return PGTG_E_INVALID;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  unsigned long long c[4];
-  HIPCHK(h, hipMemcpy(c, h->S.counters, sizeof c, hipMemcpyDeviceToHost));
-  *served = c[3];
-  return PGTG_OK;
-}
-
 int pgtg_error_count(pgtg_handle* h, uint64_t* n_errors, int32_t* first_code) {
   if (!h) return PGTG_E_INVALID;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (int rc = host_sync(h)) return rc;
   std::vector<uint8_t> e(h->n);
   HIPCHK(h, hipMemcpy(e.data(), h->S.err, h->n, hipMemcpyDeviceToHost));
   uint64_t cnt = 0;
@@ -6511,8 +6487,7 @@ int pgtg_measure_hbm(int32_t device, uint64_t bytes, int32_t reps, double* copy_
   void *a = nullptr, *b = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   int rc = PGTG_E_DEVICE;
-  int ncu = 256;
-  (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
+  const int ncu = cu_count(device);
   double best = 0.0;
   if (hipMalloc(&a, n16 * 16) == hipSuccess && hipMalloc(&b, n16 * 16) == hipSuccess &&
       hipMemset(a, 1, n16 * 16) == hipSuccess && hipMemset(b, 2, n16 * 16) == hipSuccess &&
@@ -6559,18 +6534,14 @@ int pgtg_window(const pgtg_handle* h) { return h ? h->hcfg.win : 0; }
 uint64_t pgtg_num_envs(const pgtg_handle* h) { return h ? h->n : 0; }
 const char* pgtg_step_kernel(const pgtg_handle* h) {
   if (!h) return "";
-  const bool big = h->hcfg.nt > kSmallTiles;
-  if (h->hcfg.need_car) return big ? "pgtg::k_env<true, true> + pgtg::k_traffic" : "pgtg::k_env<true, false> + pgtg::k_traffic";
-  if (h->hcfg.n_rules > 0) return big ? "pgtg::k_env<true, true>" : "pgtg::k_env<true, false>";
-  if (h->L.queue && h->q_block == 1) return big ? "pgtg::k_envb<true>" : "pgtg::k_envb<false>";
-  if (h->L.queue) return big ? "pgtg::k_envq<true>" : "pgtg::k_envq<false>";
-  return big ? "pgtg::k_env<false, true>" : "pgtg::k_env<false, false>";
+  const StepKernel& k = step_fn(h, MODE_STEP);  // the kernel launch() picks
+  return h->hcfg.need_car ? k.name_traffic : k.name;
 }
 
 int pgtg_occupancy(const pgtg_handle* h, int32_t* step_blocks_per_cu) {
   if (!h) return PGTG_E_INVALID;
   int nb = 0;
-  const void* fn = step_fn(h, MODE_STEP);  // the kernel launch() picks
+  const void* fn = step_fn(h, MODE_STEP).fn;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kBlock, h->lds) != hipSuccess) return PGTG_E_DEVICE;
   if (step_blocks_per_cu) *step_blocks_per_cu = nb;
   return PGTG_OK;
