@@ -179,6 +179,14 @@ int pgtg_create(const PgtgConfig* cfg, uint64_t n_envs, int32_t device, pgtg_han
 int pgtg_destroy(pgtg_handle* h);
 /* Queue work on this stream (hipStream_t); NULL = the null stream. */
 int pgtg_set_stream(pgtg_handle* h, void* stream);
+/* Bind the output buffers.  Between step launches the bound `obs` buffer belongs to the handle: the persistent
+ * map-queue step kernel (k_envq) writes only the observations that changed since the last launch (whole
+ * 128-byte lines) and relies on the other bytes being the ones it wrote before.  A caller that wrote into `obs`
+ * calls pgtg_observe or binds the outputs again before the next step; reading it is always fine.  Every
+ * call that changes an env's state or the binding without rewriting all observations (this one, a masked
+ * reset, pgtg_set_agent, pgtg_add_car, pgtg_set_to_state, pgtg_load_state, pgtg_snapshot_load,
+ * pgtg_set_rules) makes the next step write every observation, so a step right after one of them returns
+ * correct observations without pgtg_observe.  final_obs and every other output are written in full. */
 int pgtg_set_outputs(pgtg_handle* h, const PgtgOutputs* out);
 /* Seeded reset of env i with seeds_host[i] (NULL: seed_base + global index), only where
  * mask_dev[i] != 0 (NULL: all).  Writes the reset observation to the bound outputs. */

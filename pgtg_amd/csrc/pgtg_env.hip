@@ -2767,6 +2767,22 @@ __device__ __forceinline__ void write_obs(uint8_t* __restrict__ dst, uint32_t cn
   }
 }
 
+// Everything an env's observation is a function of on build_obs's one-tile fast path without traffic,
+// as one word: the agent's tile, that tile's plan word, its used-subgoal bit, the light colour where the
+// tile holds a light, and the episode's start/goal word.  The position inside the tile is not among them.
+// Two equal keys of one env mean byte-identical observations; obs_key_ok says whether the configuration
+// is on that path at all.
+__device__ __forceinline__ bool obs_key_ok(const DevCfg& c) { return !c.sliding && !c.generic_channels && !c.need_car; }
+template <bool BIG>
+__device__ __forceinline__ uint64_t obs_key(const DevCfg& c, const EnvView& v, const Plan& pl) {
+  const int pix = min(max(0, v.px), c.W - 1), piy = min(max(0, v.py), c.H - 1);
+  const int t = (piy / kTile) * c.tw + pix / kTile;
+  const uint32_t p = pl[t];  // (16 bits)
+  const uint32_t col = plan_otype(p) == 4u ? (uint32_t)phase_color(c, v.phase) : 0u;
+  const uint32_t lo = p | (used_bit<BIG>(v, p, t) ? 1u << 16 : 0u) | col << 17 | (uint32_t)t << 19;
+  return (uint64_t)v.sg << 32 | lo;
+}
+
 // ------------------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------------------
@@ -2822,6 +2838,12 @@ constexpr uint64_t kStaggerMaxTicks = 20000;  // 200 us of 100 MHz wall clock: a
 constexpr int kBlockDepth = 3;   // of k_envb (the rings refilled per block)
 constexpr uint32_t kQueueStale = 0x80u;  // qstate flag: the ring's entries are not this env's (k_qfill)
 constexpr int kViewDw = 8;       // k_envq with <= 32 envs: an env's view words for the image builders
+// k_envq's line masks of the changed observations (lm_words words each), in LDS it leaves unused: the reset
+// hand-over words (scratch_dw per env, k_env's).  Two, one per block parity: its waves read a block's mask in
+// its last phase (the observation write) and no barrier separates that from the next block's clear, so the
+// next block clears and marks the other one (whose readers are two barriers behind).
+constexpr int kObsMasks = 2;
+constexpr uint32_t kQselFull = 8u;  // k_envq's qsel: write every observation line (the buffer is not current)
 
 // a ring entry's spawn tag (its last word): the spawn counter it was generated for, inverted so that
 // zeroed memory matches none
@@ -3504,7 +3526,7 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
   const bool env_wave = wave < env_waves;
   // refill requests: this launch's into list qsel & 3 (buffer qsel >> 2), the previous launch's from
   // list (qsel + 2) % 3 (the other buffer); the third list's counters are cleared for the next launch
-  const uint32_t par = qsel >> 2;
+  const uint32_t par = (qsel >> 2) & 1u;
   const uint64_t nblk = (S.n + (uint64_t)L.envs - 1) / (uint64_t)L.envs;
   const uint64_t cap = queue_req_cap(nblk, gridDim.x, L.envs);  // requests per workgroup and launch
   uint2* req_new = S.qreq + ((uint64_t)par * gridDim.x + blockIdx.x) * cap;
@@ -3533,6 +3555,12 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
   uint32_t* ctr = reinterpret_cast<uint32_t*>(sel + kBlock);  // sub_barrier counter
   uint32_t* lm = L.lm_words ? reinterpret_cast<uint32_t*>(sel + kBlock + 128) : nullptr;  // terminal lines
   uint32_t* vw = reinterpret_cast<uint32_t*>(sel + kBlock + 128) + L.lm_words;  // env views (<= 32 envs)
+  // Only the observation lines of envs whose observation changed are written (obs_key; an env that
+  // finished, or failed, counts as changed): the others' bytes are in out.obs already, which the host
+  // vouches for by leaving kQselFull clear.  Other configurations write every line.
+  const bool delta = lm && out.obs && obs_key_ok(c) && !(qsel & kQselFull) && kObsMasks * L.lm_words <= L.scratch_dw * L.envs;
+  uint32_t* const om0 = lds + L.envs * pdw;  // (the hand-over words: see kObsMasks)
+  uint32_t* om = delta ? om0 : nullptr;  // this block's changed-observation lines (alternating)
   uint32_t* qn = ctr + 1;  // this launch's requests so far
   uint32_t* nxt = ctr + 2;  // the next block
   // blocks after the first: taken from a counter (three, rotating: this launch's, the next one's
@@ -3642,7 +3670,9 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
       stage_plan<BIG>(reinterpret_cast<const uint16_t*>(ring_slot(queue_cur(qs))), c.plan_dq, plan_w, pdw);  // the cur slot
     }
     for (int k = rank; k < L.lm_words; k += nthr) lm[k] = 0u;
-    sub_barrier(ctr, bar += (uint32_t)np);  // plans, line mask (and the last block's images written)
+    if (om)
+      for (int k = rank; k < L.lm_words; k += nthr) om[k] = 0u;
+    sub_barrier(ctr, bar += (uint32_t)np);  // plans, line masks (and the last block's images written)
     STAMP(1);
     uint8_t my_sel = 0;
     int err = 0;
@@ -3650,6 +3680,7 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
       StepResult res{0.0, 0.0, 0u};
       bool occ_sat = false;
       TrafState ts{0, 0, 0, 0};
+      const uint64_t key0 = om ? obs_key<BIG>(c, v, pl) : 0ull;  // of the observation out.obs holds
       err = env_step<false, BIG>(c, S, i, v, pl, act, res, nullptr, occ_sat, nullptr, ts, nullptr);
       STAMP(22);
       const bool done = (v.flags & (kFlagTerminated | kFlagTruncated)) != 0;
@@ -3662,6 +3693,8 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
       if (BIG && res.plan_dirty && !my_sel)  // used subgoals (kPlanUsed), into the cur slot's plan quads
         store_plan_quads(c, reinterpret_cast<uint4*>(ring_slot(queue_cur(qs))), c.plan_dq, plan_w, pdw);
       if (lm && my_sel && out.final_obs) mark_lines(lm, out.final_obs + env0 * (uint64_t)c.obs_bytes, (uint32_t)slot, (uint32_t)c.obs_bytes);
+      if (om && (my_sel || err != 0 || obs_key<BIG>(c, v, pl) != key0))
+        mark_lines(om, out.obs + env0 * (uint64_t)c.obs_bytes, (uint32_t)slot, (uint32_t)c.obs_bytes);
       STAMP(23);
     }
     // the post-step image of every env (terminal for the finished ones)
@@ -3772,7 +3805,8 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
       S.qctr[par * gridDim.x + blockIdx.x] = one_round ? min(*qn, (uint32_t)kQueueLanes) : *qn;
     const uint32_t g = *nxt;  // (published after the step, rewritten after the next block's first barrier)
     if (out.obs && !ABLATE(L, 4))
-      write_obs(out.obs + env0 * (uint64_t)c.obs_bytes, (uint32_t)nb, (uint32_t)c.obs_bytes, st, nullptr, rank, nthr);
+      write_obs(out.obs + env0 * (uint64_t)c.obs_bytes, (uint32_t)nb, (uint32_t)c.obs_bytes, st, nullptr, rank, nthr, om);
+    if (om) om = om == om0 ? om0 + L.lm_words : om0;  // (the other mask: see kObsMasks)
     if (tid == 0) atomicAdd(&S.counters[0], (unsigned long long)nb);
     if (blk == blockIdx.x) stagger_record(L, S, t_start);
     STAMP(6);
@@ -4636,6 +4670,10 @@ struct pgtg_handle {
   int q_block = -1;
   bool slot_plan = false;  // a k_envq handle: no S.plan, an env's plan is the cur slot of its ring
   int tune_queue_mode = 0;  // PgtgConfig.tune_queue_mode
+  // The bound obs buffer holds every env's current observation: set by a launch that wrote them all,
+  // cleared by whatever changes an env's state, the output binding or the step kernel without rewriting
+  // them.  k_envq then writes only the lines of the observations that changed (obs_key).
+  bool obs_current = false;
   // FlattenObservation rows after every launch (pgtg_set_flat_outputs): k_flatten's arguments
   FlatArgs flat{};
   const void* flat_fn = nullptr;  // k_flatten variant of the last launch, and its resident workgroups
@@ -5096,6 +5134,7 @@ extern "C" {
 // 0 = automatic) force shapes for tests and A/B runs.
 static int choose_launch(pgtg_handle* h, bool allow_queue) {
   const DevCfg& c = h->hcfg;
+  h->obs_current = false;  // (another layout, maybe another step kernel)
   const uint64_t n_envs = h->n;
   // envs per 256-lane workgroup.  A workgroup's time is the slowest of its lanes' serial chains, so
   // small batches use fewer envs per workgroup to reach every CU; large batches of maps of >= 16
@@ -5376,6 +5415,7 @@ int pgtg_set_outputs(pgtg_handle* h, const PgtgOutputs* o) {
   if (h->ep.out_ret && (!o->reward || !o->terminated || !o->truncated))  // (k_episode checks no pointer)
     return fail(h, PGTG_E_INVALID, "episode statistics are bound: the reward, terminated and truncated outputs must stay");
   h->out = *o;
+  h->obs_current = false;  // (another buffer, or one the caller wrote into)
   return PGTG_OK;
 }
 
@@ -5462,7 +5502,9 @@ static int launch(pgtg_handle* h, const uint8_t* actions, const uint8_t* mask, i
     HIPCHK(h, hipEventRecord(h->evpool[h->ev_used], h->stream));
   }
   const StepKernel& k = step_fn(h, mode);
-  uint32_t qsel = (uint32_t)(h->q_launch % 3) | (uint32_t)(h->q_launch & 1) << 2;  // k_envq: its rotating lists
+  const bool full = !h->obs_current;  // (k_envq) every observation line is written
+  h->obs_current = false;                    // (until this launch and what follows it have gone out)
+  uint32_t qsel = (uint32_t)(h->q_launch % 3) | (uint32_t)(h->q_launch & 1) << 2 | (full ? kQselFull : 0u);  // k_envq: its rotating lists
   void* args[] = {&h->dcfg, &h->dtab, &h->S, &actions, &mask, &h->out, &mode, &h->L, &h->tr_slot};
   void* bargs[] = {&h->dcfg, &h->dtab, &h->S, &actions, &h->out, &h->L};
   void* qargs[] = {&h->dcfg, &h->dtab, &h->S, &actions, &h->out, &h->L, &qsel};
@@ -5497,6 +5539,8 @@ static int launch(pgtg_handle* h, const uint8_t* actions, const uint8_t* mask, i
   }
   if (h->ep.out_ret && mode == MODE_STEP)
     if (int rc = launch_episode(h)) return rc;
+  // every env's observation went out: a step, pgtg_observe, a reset of every env
+  h->obs_current = h->out.obs != nullptr && (mode == MODE_STEP || mode == MODE_OBSERVE || !mask);
   return PGTG_OK;
 }
 
@@ -5759,6 +5803,7 @@ int pgtg_set_rules(pgtg_handle* h, const PgtgRule* rules, int32_t n_rules) {
   if (!h || n_rules < 0 || n_rules > PGTG_MAX_RULES || (n_rules > 0 && !rules))
     return h ? fail(h, PGTG_E_INVALID, "bad rule count") : PGTG_E_INVALID;
   if (int rc = host_sync(h)) return rc;
+  h->obs_current = false;
   DevCfg& c = h->hcfg;
   const DevCfg old_cfg = c;
   const Lds old_L = h->L;
@@ -5791,6 +5836,7 @@ int pgtg_set_rules(pgtg_handle* h, const PgtgRule* rules, int32_t n_rules) {
 int pgtg_set_agent(pgtg_handle* h, uint64_t env, int32_t x, int32_t y, int32_t vx, int32_t vy) {
   if (!h || env >= h->n) return PGTG_E_INVALID;
   if (int rc = host_sync(h)) return rc;
+  h->obs_current = false;
   EnvRec r;
   HIPCHK(h, hipMemcpy(&r, h->S.rec + env, sizeof r, hipMemcpyDeviceToHost));
   r.a.x = ((uint32_t)x & 0xffffu) | ((uint32_t)y << 16);
@@ -5809,6 +5855,7 @@ int pgtg_add_car(pgtg_handle* h, uint64_t env, int32_t x, int32_t y, int32_t rou
   if (!h->hcfg.need_car) return fail(h, PGTG_E_UNSUPPORTED, "create the handle with min_car_capacity > 0 or traffic");
   if (!car_ok(h->hcfg, x, y, route, profile)) return fail(h, PGTG_E_INVALID, "car outside the map or bad route/profile");
   if (int rc = host_sync(h)) return rc;
+  h->obs_current = false;
   uint4 t;
   if (int rc = read_traf(h, env, &t)) return rc;
   std::vector<PgtgCar> v;
@@ -5979,6 +6026,7 @@ int pgtg_load_state(pgtg_handle* h, const void* buf, uint64_t bytes) {
     if (e.id != s.id || e.bytes != s.bytes) return fail(h, PGTG_E_INVALID, "pgtg_load_state: section table mismatch");
   }
   if (int rc = host_sync(h)) return rc;
+  h->obs_current = false;  // (outputs are not state: out.obs still shows the envs replaced)
   for (const auto& s : v) {
     off = (off + 15) & ~15ull;
     HIPCHK(h, hipMemcpy(s.ptr, p + off, s.bytes, hipMemcpyHostToDevice));
@@ -6114,6 +6162,7 @@ static int snapshot_copy(pgtg_handle* h, const pgtg_snapshot* s, bool to_snapsho
   // queue_fill) until the next step launch: nothing is left to zero after the copy.  The k_traffic
   // work list is written and consumed inside one step launch, so none is pending either.
   if (int rc = queue_fill(h)) return rc;
+  if (!to_snapshot) h->obs_current = false;  // (outputs are not state)
   T.src_idx = src_idx;
   T.dst_idx = dst_idx;
   T.count = count;
@@ -6152,6 +6201,7 @@ int pgtg_set_to_state(pgtg_handle* h, uint64_t env, int32_t x, int32_t y, int32_
     if (!car_ok(c, cars[k].x, cars[k].y, cars[k].route, cars[k].profile))
       return fail(h, PGTG_E_INVALID, "car outside the map or bad route/profile");
   if (int rc = host_sync(h)) return rc;
+  h->obs_current = false;
   EnvRec r;
   HIPCHK(h, hipMemcpy(&r, h->S.rec + env, sizeof r, hipMemcpyDeviceToHost));
   r.a.x = ((uint32_t)x & 0xffffu) | ((uint32_t)y << 16);
