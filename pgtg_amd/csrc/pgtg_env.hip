@@ -1588,6 +1588,27 @@ __device__ __forceinline__ void store_initial_counters(const DevCfg& c, const De
   for (int w = sub; w < nw; w += g) fo[w] = cnt[w];
 }
 
+// The single definition of a new episode's visited-square bitmap: all clear but the start square.
+__device__ __forceinline__ void visited_begin(const DevCfg& c, const DevState& S, uint64_t i, const EnvView& v) {
+  if (!S.visited) return;
+  uint32_t* vis = S.visited + i * (uint64_t)c.vis_words;
+  for (int q2 = 0; q2 < c.vis_words; q2++) vis[q2] = 0;
+  int b = (v.px + 2) * c.vis_pitch + (v.py + 2);
+  vis[b >> 5] |= 1u << (b & 31);
+}
+
+// The single definition of the obstacle streams of the episode with spawn counter k: ice, broken road
+// and sand from the seed pool's children k + 2, k + 3, k + 4 (k + 0: the map, k + 1: the cars).
+__device__ __forceinline__ void episode_streams(const DevCfg& c, const DevState& S, uint64_t i, const SeedPool& sp, uint32_t k) {
+  if (c.need_ice) stream_store_all(S.ice, i, ss_child(sp, k + 2u));
+  if (c.need_broken) stream_store_all(S.broken, i, ss_child(sp, k + 3u));
+  if (c.need_sand) stream_store_all(S.sand, i, ss_child(sp, k + 4u));
+}
+// (the reset paths that take a generated map need the seed pool for these streams only)
+__device__ __forceinline__ void episode_streams(const DevCfg& c, const DevState& S, uint64_t i, uint32_t k) {
+  if (c.need_ice || c.need_broken || c.need_sand) episode_streams(c, S, i, ss_pool(S.seed[i]), k);
+}
+
 // The full per-env reset.  `key` = spawn counter (5 children per episode).  Returns 0 or -code.
 template <bool TR, bool BIG>
 __device__ __forceinline__ int env_reset(const DevCfg& c, const DevState& S, uint64_t i, EnvView& v, uint16_t* plan,
@@ -1599,9 +1620,7 @@ __device__ __forceinline__ int env_reset(const DevCfg& c, const DevState& S, uin
   Pcg map_rng = ss_child(sp, k + 0u);
   Pcg car_rng;
   if ((TR && c.need_car)) car_rng = ss_child(sp, k + 1u);
-  if (c.need_ice) stream_store_all(S.ice, i, ss_child(sp, k + 2u));
-  if (c.need_broken) stream_store_all(S.broken, i, ss_child(sp, k + 3u));
-  if (c.need_sand) stream_store_all(S.sand, i, ss_child(sp, k + 4u));
+  episode_streams(c, S, i, sp, k);
   v.spawn = k + 5u;
   STAMP(9);
   int st_t, st_d, gl_t, gl_d;
@@ -1645,12 +1664,7 @@ __device__ __forceinline__ int env_reset(const DevCfg& c, const DevState& S, uin
   v.px = tx * kTile + lx;
   v.py = ty * kTile + ly;
   STAMP(12);
-  if (S.visited) {
-    uint32_t* vis = S.visited + i * (uint64_t)c.vis_words;
-    for (int q2 = 0; q2 < c.vis_words; q2++) vis[q2] = 0;
-    int b = (v.px + 2) * c.vis_pitch + (v.py + 2);
-    vis[b >> 5] |= 1u << (b & 31);
-  }
+  visited_begin(c, S, i, v);
   if ((TR && c.need_car)) {  // the cars are created by k_traffic from this stream
     stream_store_all(S.car, i, car_rng);
     ts = TrafState{0, 0, 0, 0};
@@ -3306,6 +3320,30 @@ __global__ void __launch_bounds__(kBlock, TR ? 3 : 4) k_env(const DevCfg* __rest
 // start square -- depends only on (seed, spawn counter), not on the episode before it, so the next
 // two episodes' maps of every env are generated ahead and a reset takes the head of the env's ring.
 // ------------------------------------------------------------------------------------------------
+// EnvView::sg, the start/goal word of a map: start tile, start direction, goal tile, goal direction
+__device__ __forceinline__ uint32_t sg_word(int st_t, int st_d, int gl_t, int gl_d) {
+  return (uint32_t)st_t | (uint32_t)st_d << 8 | (uint32_t)gl_t << 16 | (uint32_t)gl_d << 24;
+}
+// A generated map's meta quad, packed and read in one place for k_envb and the fill kernels: start square px | py << 16, start/goal word,
+// path length | -error << 16, and the tag of the spawn counter the map was made for.  It is the 16 bytes
+// behind the tile plan of a map-ring entry: gen_queue_entry packs it, ring_take returns it to k_envb.
+// (k_envq reads the same quad and k_env's compacted reset hands its first three words over in LDS, both
+// still by hand: DESIGN.md, "Shared definitions of an episode's start".)
+struct QueueMeta {
+  uint32_t pos, sg, len_err, tag;
+  __device__ __forceinline__ explicit QueueMeta(const uint4& q) : pos(q.x), sg(q.y), len_err(q.z), tag(q.w) {}
+  static __device__ __forceinline__ uint4 pack(int px, int py, uint32_t sg, uint32_t len, int err, uint32_t k) {
+    return make_uint4(((uint32_t)px & 0xffffu) | ((uint32_t)py << 16), sg, len | (uint32_t)(-err) << 16, queue_tag(k));
+  }
+  __device__ __forceinline__ uint32_t path_len() const { return len_err & 0xffffu; }
+  __device__ __forceinline__ int gen_err() const { return -(int)(len_err >> 16); }  // the generation's error
+  // ... and the error of taking the entry for spawn counter k0: it was generated for that episode -- the
+  // queue kernels see to it that it always is -- so a mismatch is reported as a device error, never used
+  __device__ __forceinline__ int err(uint32_t k0, bool ablate) const {
+    return (tag != queue_tag(k0) && !ablate) ? PGTG_E_DEVICE : gen_err();
+  }
+};
+
 // One ring entry: generate_map + compile_path + the start draw of env_reset for spawn counter `k`,
 // built in the lane's LDS plan scratch and written to HBM.
 template <bool BIG>
@@ -3370,9 +3408,7 @@ __device__ __forceinline__ void gen_queue_entry(const DevCfg& c, const DevState&
     }
     d4[q] = make_uint4(wv[0], wv[1], wv[2], wv[3]);
   }
-  d4[pwords / 4] = make_uint4(((uint32_t)px & 0xffffu) | ((uint32_t)py << 16),
-                              (uint32_t)st_t | (uint32_t)st_d << 8 | (uint32_t)gl_t << 16 | (uint32_t)gl_d << 24,
-                              (uint32_t)len | (uint32_t)(-err) << 16, queue_tag(k));
+  d4[pwords / 4] = QueueMeta::pack(px, py, sg_word(st_t, st_d, gl_t, gl_d), (uint32_t)len, err, k);
   for (int q = pwords / 4 + 1; q < c.qrec_dw / 4; q++) d4[q] = make_uint4(0u, 0u, 0u, 0u);  // the line's rest
 }
 
@@ -3475,7 +3511,7 @@ __device__ __forceinline__ void group_obs(const DevCfg& c, const DevState& S, co
 // (slot qh, made for spawn counter k0) becomes its episode -- the tile plan into its HBM row and its LDS row, the obstacle streams of the episode, and
 // {px | py << 16, start/goal word, path length | error << 16} returned (env_reset without the generation).
 template <bool BIG>
-__device__ __forceinline__ uint3 ring_take(const DevCfg& c, const DevState& S, const Lds& L, uint64_t i, uint32_t qh,
+__device__ __forceinline__ QueueMeta ring_take(const DevCfg& c, const DevState& S, const Lds& L, uint64_t i, uint32_t qh,
                                            uint32_t k0, uint32_t* plan_w, int pdw, int depth) {
   const uint4* q4 = reinterpret_cast<const uint4*>(S.qbuf + (i * (uint64_t)depth + qh) * (uint64_t)c.qrec_dw);
   uint4* dstp = reinterpret_cast<uint4*>(S.plan + i * (uint64_t)c.plan_stride);
@@ -3500,16 +3536,8 @@ __device__ __forceinline__ uint3 ring_take(const DevCfg& c, const DevState& S, c
   }
   if (!ABLATE(L, 32))
     for (int k = nq; k < c.plan_stride / 8; k++) dstp[k] = make_uint4(0u, 0u, 0u, 0u);  // the row's whole lines
-  if (c.need_ice || c.need_broken || c.need_sand) {
-    SeedPool sp = ss_pool(S.seed[i]);
-    if (c.need_ice) stream_store_all(S.ice, i, ss_child(sp, k0 + 2u));
-    if (c.need_broken) stream_store_all(S.broken, i, ss_child(sp, k0 + 3u));
-    if (c.need_sand) stream_store_all(S.sand, i, ss_child(sp, k0 + 4u));
-  }
-  // the entry was generated for this episode (spawn counter k0): k_envb refills every empty head before
-  // the take, so it always is -- a mismatch is reported as a device error, never used
-  const int e2 = (meta.w != queue_tag(k0) && !ABLATE(L, 1 | 16)) ? PGTG_E_DEVICE : -(int)(meta.z >> 16);
-  return make_uint3(meta.x, meta.y, (meta.z & 0xffffu) | (uint32_t)(-e2) << 16);
+  episode_streams(c, S, i, k0);
+  return QueueMeta(meta);
 }
 
 template <bool BIG>
@@ -3986,25 +4014,21 @@ __global__ void __launch_bounds__(kBlock, 4) k_envb(const DevCfg* __restrict__ c
   const bool reset_now = my_sel != 0;
   if (reset_now) {  // the ring's head becomes the episode (env_reset without the generation)
     const uint32_t k0 = v.spawn;
-    const uint3 tk = ring_take<BIG>(c, S, L, i, qh, k0, plan_w, pdw, kBlockDepth);
+    const QueueMeta m = ring_take<BIG>(c, S, L, i, qh, k0, plan_w, pdw, kBlockDepth);
     v.spawn = k0 + 5u;
-    v.sg = tk.y;
+    v.sg = m.sg;
     v.used = 0;
-    v.path_len = tk.z & 0xffffu;
+    v.path_len = m.path_len();
     v.flags = 0;
     v.phase = 0;
     v.elapsed = 0;
     v.vx = v.vy = 0;
-    v.px = (int)(int16_t)(tk.x & 0xffffu);
-    v.py = (int)(int16_t)(tk.x >> 16);
-    const int e2 = -(int)(tk.z >> 16);
+    v.px = (int)(int16_t)(m.pos & 0xffffu);
+    v.py = (int)(int16_t)(m.pos >> 16);
+    // (the helper refilled every empty head before the take, so the entry is this episode's)
+    const int e2 = m.err(k0, ABLATE(L, 1 | 16));
     if (e2) err = e2;
-    if (S.visited && e2 == 0) {
-      uint32_t* vis = S.visited + i * (uint64_t)c.vis_words;
-      for (int q2 = 0; q2 < c.vis_words; q2++) vis[q2] = 0;
-      int b = (v.px + 2) * c.vis_pitch + (v.py + 2);
-      vis[b >> 5] |= 1u << (b & 31);
-    }
+    if (e2 == 0) visited_begin(c, S, i, v);
   }
   STAMP(4);
   if (live) {
@@ -4043,6 +4067,13 @@ __global__ void __launch_bounds__(kBlock, 4) k_envb(const DevCfg* __restrict__ c
 }
 
 
+// The single definition of how a fill kernel counts the maps it generated (S.counters[2]): `made` is the
+// lane's count, 0 .. 3, summed over the wave from two ballots; one atomic per wave.
+__device__ __forceinline__ void count_maps(const DevState& S, uint32_t made) {
+  const uint32_t wsum = (uint32_t)__popcll(__ballot(made & 1u)) + 2u * (uint32_t)__popcll(__ballot(made & 2u));
+  if ((threadIdx.x & 63) == 0 && wsum) atomicAdd(&S.counters[2], (unsigned long long)wsum);
+}
+
 // Fill every env's map ring: after a reset launch (whose k_env generated the current episodes' maps
 // and marked the reset envs' rings stale), a state dump (the requests still pending) or a change of
 // step kernel.  One lane per env checks the head's and the spare's spawn tags against the env's next two
@@ -4078,9 +4109,7 @@ __global__ void __launch_bounds__(kBlock) k_qfill(const DevCfg* __restrict__ cfg
     }
     if (stale) S.qstate[i] = (uint8_t)(qc | qh << 2);
   }
-  // maps generated (S.counters[2]): one atomic per wave
-  const uint32_t wsum = (uint32_t)__popcll(__ballot(made & 1u)) + 2u * (uint32_t)__popcll(__ballot(made & 2u));
-  if ((threadIdx.x & 63) == 0 && wsum) atomicAdd(&S.counters[2], (unsigned long long)wsum);
+  count_maps(S, made);
 }
 
 // k_qfill for k_envb's rings (three entries; qstate = held | head << 2, kQueueStale: none held): the
@@ -4107,9 +4136,7 @@ __global__ void __launch_bounds__(kBlock) k_qfill_b(const DevCfg* __restrict__ c
       made = (uint32_t)kBlockDepth - qn;
     }
   }
-  // maps generated (S.counters[2]): one atomic per wave
-  const uint32_t wsum = (uint32_t)__popcll(__ballot(made & 1u)) + 2u * (uint32_t)__popcll(__ballot(made & 2u));
-  if ((threadIdx.x & 63) == 0 && wsum) atomicAdd(&S.counters[2], (unsigned long long)wsum);
+  count_maps(S, made);
 }
 
 #ifdef PGTG_STAMPS

@@ -42,6 +42,8 @@ CALLER = dict(random_map_width=4, random_map_height=4, random_map_obstacle_proba
               reckless_driver_percentage=0.05, sliding_observation_window_size=5, max_allowed_deviation=15,
               use_sliding_observation_window=True, use_next_subgoal_direction=True, final_goal_bonus=200,
               standing_still_penalty=1)
+OBST_VISITED = dict(random_map_width=3, random_map_height=3, random_map_obstacle_probability=1.0,
+                    already_visited_position_penalty=0.25)
 FIXED_MAP = os.path.join(helpers.TESTDATA, "4x1_map.json")
 
 K_ENV, K_ENVQ, K_ENVB = "pgtg::k_env<false, false>", "pgtg::k_envq<false>", "pgtg::k_envb<false>"
@@ -75,6 +77,17 @@ CASES = {
     "traffic_serial_L2": (TRAFFIC, 512, 8, 2, dict(kt_grid=8, kt_serial=1), K_TRAFFIC, None, 1000),
     "caller_L10": (CALLER, 2048, 25, 10, None, K_TRAFFIC, None, 1000),
     "caller_L100": (CALLER, 512, 110, 100, None, K_TRAFFIC, None, 1000),
+    # What every reset path shares -- the obstacle streams of the new episode, its visited bitmap, its
+    # start square and record -- through each step kernel: every square an obstacle, a penalty for visited
+    # squares, and a limit under which every env resets six times or more in 20 ticks.  64 envs in
+    # workgroups of 32 (the group-built images); 33 in one workgroup (a partly filled wave, an image
+    # per lane); k_env's 256-env workgroup runs its resets compacted.
+    "envq_obstacles_visited_L4": (OBST_VISITED, 64, 20, 4, dict(envs_per_block=32, queue_mode=1), K_ENVQ, 32, 1000),
+    "envb_obstacles_visited_L4": (OBST_VISITED, 64, 20, 4, dict(envs_per_block=32, queue_mode=2), K_ENVB, 32, 1000),
+    "env_obstacles_visited_L4": (OBST_VISITED, 64, 20, 4, dict(envs_per_block=256), K_ENV, 256, 1000),
+    "envq_obstacles_visited_33_L4": (OBST_VISITED, 33, 20, 4, dict(envs_per_block=64, queue_mode=1), K_ENVQ, 64, 1000),
+    "envb_obstacles_visited_33_L4": (OBST_VISITED, 33, 20, 4, dict(envs_per_block=64, queue_mode=2), K_ENVB, 64, 1000),
+    "env_obstacles_visited_33_L4": (OBST_VISITED, 33, 20, 4, dict(envs_per_block=256), K_ENV, 256, 1000),
 }
 
 
