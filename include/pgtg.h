@@ -398,6 +398,49 @@ int pgtg_policy_packed_bytes(uint64_t obs_dim, uint64_t* bytes);
 int pgtg_policy_pack(pgtg_handle* h, const PgtgPolicyWeights* raw, void* packed);
 int pgtg_policy(pgtg_handle* h, const PgtgPolicy* a);
 int pgtg_policy_chunk(void);
+/* One minibatch of SB3's PPO.train (defaults; clip_range_vf = None) over a finished rollout of int8 rows
+ * (new; no reference function: it replaces the forward, the loss and loss.backward() of the PPO("MlpPolicy")
+ * of pgtg/train.py:61-74).  Sample s = 0 .. batch-1 is (env, step) = (indices[s] / steps, indices[s] % steps),
+ * SB3's swap_and_flatten order; its row starts at byte step * obs_pitch + env * obs_dim of obs (any base
+ * alignment; no load touches a byte outside [obs, obs + (steps-1) * obs_pitch + n * obs_dim)); repeats are
+ * allowed; the [batch, obs_dim] matrix is never materialised.  With logits, value the forward of pgtg_policy
+ * (the same tiling and order of operations) under `packed`, a = actions[step][env], and every mean over batch:
+ *   adv   = adv_stats ? (advantages - adv_stats[0]) * adv_stats[1] : advantages
+ *   ratio = exp(log_prob(a) - log_probs[step][env])
+ *   policy_loss  = mean(-min(adv ratio, adv clamp(ratio, 1 - clip_range, 1 + clip_range)))
+ *   value_loss   = mean((returns - value)^2)        entropy_loss = -mean(-sum_c p_c log p_c)
+ *   loss = policy_loss + ent_coef entropy_loss + vf_coef value_loss
+ * and d loss / d(every one of the twelve tensors) is written (not accumulated) into grads, float32 in SB3's
+ * nn.Linear layouts (PgtgPolicyWeights); the min passes adv where its unclipped branch is the smaller or the
+ * ratio lies inside the clip interval, and 0 otherwise.  stats[8] (device): loss, policy_loss, value_loss,
+ * entropy_loss, approx_kl = mean((ratio - 1) - log ratio), clip fraction = mean(|ratio - 1| > clip_range), 0, 0.
+ * An index outside [0, steps * n), or a sample whose action is above 8, is not dereferenced: the sample adds
+ * nothing to any sum (the means stay over batch) and sets the handle's error byte s mod its batch size to
+ * -PGTG_E_INVALID (pgtg_error_count).  Three launches (k_ppo_loss, k_ppo_dw1, k_ppo_reduce), asynchronous on
+ * the handle's stream, no atomics: the partition of the work is a function of (batch, obs_dim) alone and every
+ * sum runs in a fixed order, so the same call gives the same bits.  workspace: pgtg_ppo_workspace_bytes bytes,
+ * 16-byte aligned, contents irrelevant.  A NULL required pointer (adv_stats alone may be NULL), obs_dim outside
+ * [1, PGTG_POLICY_MAX_OBS_DIM], steps or n of 0, obs_pitch < n * obs_dim, packed or workspace not 16-byte
+ * aligned, products that overflow, a non-finite coefficient: PGTG_E_INVALID with a message, nothing launched.
+ * batch == 0 is a no-op. */
+typedef struct {
+  float *w1p, *b1p, *w2p, *b2p, *wa, *ba;
+  float *w1v, *b1v, *w2v, *b2v, *wv, *bv;
+} PgtgPpoGrads;
+typedef struct {
+  uint64_t batch, obs_dim, steps, n, obs_pitch;   /* B, D, T, N, bytes from obs[t] to obs[t+1] */
+  const int8_t* obs; const int64_t* indices;      /* indices [batch] */
+  const uint8_t* actions;                         /* [steps][n], as log_probs, advantages, returns */
+  const float *log_probs, *advantages, *returns;
+  const void* packed;                             /* pgtg_policy_pack's buffer */
+  const float* adv_stats;                         /* {mean, 1 / (std + 1e-8)} or NULL */
+  double clip_range, ent_coef, vf_coef;
+  void* workspace;
+  PgtgPpoGrads grads;
+  float* stats;                                   /* [8] */
+} PgtgPpoGrad;
+int pgtg_ppo_workspace_bytes(uint64_t obs_dim, uint64_t batch, uint64_t* bytes);
+int pgtg_ppo_grad(pgtg_handle* h, const PgtgPpoGrad* a);
 /* Re-emit the observation of every env into the bound outputs (after set_agent/add_car). */
 int pgtg_observe(pgtg_handle* h);
 /* Per-env uint64 digest of the car list into out_dev[N] (device; parity tests: the car term of

@@ -35,6 +35,7 @@ EXPORTED = [
     "pgtg_set_to_state", "pgtg_car_digest", "pgtg_get_queue_maps", "pgtg_get_queue_overflow", "pgtg_set_flat_outputs", "pgtg_set_flat_scalars",
     "pgtg_set_episode_stats", "pgtg_episode_summary", "pgtg_gae", "pgtg_flatten",
     "pgtg_policy", "pgtg_policy_pack", "pgtg_policy_packed_bytes", "pgtg_policy_chunk",
+    "pgtg_ppo_workspace_bytes", "pgtg_ppo_grad",
     "pgtg_snapshot_create", "pgtg_snapshot_destroy", "pgtg_snapshot_bytes", "pgtg_snapshot_save", "pgtg_snapshot_load",
 ]
 
@@ -117,6 +118,18 @@ class PgtgPolicy(C.Structure):
                 ("uniforms", C.c_void_p), ("actions", C.c_void_p), ("values", C.c_void_p), ("log_probs", C.c_void_p)]
 
 
+class PgtgPpoGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in POLICY_WEIGHT_FIELDS]
+
+
+class PgtgPpoGrad(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("batch", "obs_dim", "steps", "n", "obs_pitch")] + [
+        (n, C.c_void_p) for n in ("obs", "indices", "actions", "log_probs", "advantages", "returns", "packed",
+                                  "adv_stats")] + [
+        ("clip_range", C.c_double), ("ent_coef", C.c_double), ("vf_coef", C.c_double), ("workspace", C.c_void_p),
+        ("grads", PgtgPpoGrads), ("stats", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -171,6 +184,8 @@ def lib():
         "pgtg_policy_pack": ([vp, C.POINTER(PgtgPolicyWeights), vp], C.c_int),
         "pgtg_policy_packed_bytes": ([u64, C.POINTER(u64)], C.c_int),
         "pgtg_policy_chunk": ([], C.c_int),
+        "pgtg_ppo_workspace_bytes": ([u64, u64, C.POINTER(u64)], C.c_int),
+        "pgtg_ppo_grad": ([vp, C.POINTER(PgtgPpoGrad)], C.c_int),
         "pgtg_snapshot_create": ([vp, u64, C.POINTER(vp)], C.c_int),
         "pgtg_snapshot_destroy": ([vp], C.c_int),
         "pgtg_snapshot_bytes": ([vp, C.POINTER(u64), C.POINTER(u64)], C.c_int),

@@ -29,6 +29,7 @@
 #include "pgtg_episode.h"
 #include "pgtg_rollout.h"
 #include "pgtg_policy.h"
+#include "pgtg_ppo.h"
 #include "pgtg_snapshot.h"
 
 namespace pgtg {
@@ -6505,6 +6506,75 @@ int pgtg_policy(pgtg_handle* h, const PgtgPolicy* a) {
   if (a->mode == PGTG_POLICY_SAMPLE) hipLaunchKernelGGL(k_policy<POLICY_SAMPLE>, g, b, 0, h->stream, p);
   else if (a->mode == PGTG_POLICY_ARGMAX) hipLaunchKernelGGL(k_policy<POLICY_ARGMAX>, g, b, 0, h->stream, p);
   else hipLaunchKernelGGL(k_policy<POLICY_VALUE_ONLY>, g, b, 0, h->stream, p);
+  HIPCHK(h, hipGetLastError());
+  return PGTG_OK;
+}
+
+// One PPO minibatch gradient (pgtg_ppo.h): the handle gives the device, the stream, the error string and
+// the error bytes that count the skipped samples
+int pgtg_ppo_workspace_bytes(uint64_t obs_dim, uint64_t batch, uint64_t* bytes) {
+  if (!bytes || obs_dim == 0 || obs_dim > kPolMaxObsDim) return PGTG_E_INVALID;
+  if (batch > (UINT64_MAX >> 12) / obs_dim) return PGTG_E_INVALID;  // (segments <= blocks: total < 2^11 batch obs_dim floats)
+  *bytes = batch ? ppo_plan(batch, obs_dim).total * sizeof(float) : 0;
+  return PGTG_OK;
+}
+
+int pgtg_ppo_grad(pgtg_handle* h, const PgtgPpoGrad* a) {
+  if (!h) return PGTG_E_INVALID;
+  if (!a) return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: no arguments");
+  if (a->obs_dim == 0 || a->obs_dim > kPolMaxObsDim)
+    return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: obs_dim outside [1, PGTG_POLICY_MAX_OBS_DIM]");
+  if (a->steps == 0 || a->n == 0) return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: steps and n must be at least 1");
+  const PgtgPpoGrads& g = a->grads;
+  if (!a->obs || !a->indices || !a->actions || !a->log_probs || !a->advantages || !a->returns || !a->packed ||
+      !a->workspace || !a->stats)
+    return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: obs, indices, the rollout arrays, packed, workspace and stats are required");
+  if (!g.w1p || !g.b1p || !g.w2p || !g.b2p || !g.wa || !g.ba || !g.w1v || !g.b1v || !g.w2v || !g.b2v || !g.wv || !g.bv)
+    return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: all twelve gradient pointers are required");
+  if ((uintptr_t)a->packed & 15u) return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: packed must be 16-byte aligned");
+  if ((uintptr_t)a->workspace & 15u) return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: workspace must be 16-byte aligned");
+  if (a->n > (UINT64_MAX >> 1) / a->obs_dim || a->steps > (UINT64_MAX >> 1) / a->n)
+    return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: n * obs_dim or steps * n overflows");
+  if (a->obs_pitch < a->n * a->obs_dim) return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: obs_pitch is below n * obs_dim");
+  if (a->obs_pitch > (UINT64_MAX >> 1) / a->steps || (uintptr_t)a->obs > UINTPTR_MAX - a->steps * a->obs_pitch)
+    return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: steps * obs_pitch overflows");
+  if (a->batch > (UINT64_MAX >> 12) / a->obs_dim)
+    return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: batch * obs_dim overflows");
+  if (!std::isfinite(a->clip_range) || !std::isfinite(a->ent_coef) || !std::isfinite(a->vf_coef))
+    return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: clip_range, ent_coef and vf_coef must be finite");
+  if (a->batch == 0) return PGTG_OK;
+  const PpoPlan pl = ppo_plan(a->batch, a->obs_dim);
+  const uint64_t rgrid = (128 * a->obs_dim + kPpoSlot + kPpoThreads - 1) / kPpoThreads;
+  if (pl.blocks > 0x7fffffffull || pl.dtiles > 0x7fffffffull || pl.segs > 65535 || rgrid > 0x7fffffffull)
+    return fail(h, PGTG_E_UNSUPPORTED, "pgtg_ppo_grad: the batch is too large for one launch");
+  PpoArgs p;
+  p.obs = a->obs;
+  p.pitch = a->obs_pitch;
+  p.T = a->steps;
+  p.N = a->n;
+  p.D = a->obs_dim;
+  p.B = a->batch;
+  p.indices = a->indices;
+  p.actions = a->actions;
+  p.old_logp = a->log_probs;
+  p.adv = a->advantages;
+  p.ret = a->returns;
+  p.packed = (const float*)a->packed;
+  p.adv_stats = a->adv_stats;
+  p.clip = (float)a->clip_range;
+  p.clip_lo = (float)(1.0 - a->clip_range);
+  p.clip_hi = (float)(1.0 + a->clip_range);
+  p.ent_coef = (float)a->ent_coef;
+  p.vf_coef = (float)a->vf_coef;
+  p.ws = (float*)a->workspace;
+  p.err = h->S.err;
+  p.err_n = h->S.err ? h->n : 0;
+  p.g = a->grads;
+  p.stats = a->stats;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_ppo_loss, dim3((unsigned)pl.blocks), dim3(kPpoThreads), 0, h->stream, p);
+  hipLaunchKernelGGL(k_ppo_dw1, dim3((unsigned)pl.dtiles, (unsigned)pl.segs), dim3(kPpoThreads), 0, h->stream, p);
+  hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)rgrid), dim3(kPpoThreads), 0, h->stream, p);
   HIPCHK(h, hipGetLastError());
   return PGTG_OK;
 }

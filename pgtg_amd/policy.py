@@ -4,17 +4,21 @@
 categorical head and a scalar value head.  `DevicePolicy` runs its forward pass for acting as one launch
 of the HIP kernel k_policy (include/pgtg.h pgtg_policy): it reads the int8 flat rows where k_flatten left
 them and writes the action, the value and the log-probability of every env into the rows it is given --
-`Rollout.collect(policy)` is a whole rollout without a torch kernel or a host synchronisation.  The PPO
-update stays in torch: `MlpPolicyReference` is the module a trainer optimises (SB3's parameter names and
-initialisation, so a real `policy.state_dict()` loads into it), and `DevicePolicy.load_state_dict` hands
-the updated weights to the kernel by a device-side repack (k_policy_pack).
+`Rollout.collect(policy)` is a whole rollout without a torch kernel or a host synchronisation.
+`MlpPolicyReference` is the module a trainer optimises (SB3's parameter names and initialisation, so a
+real `policy.state_dict()` loads into it), and `DevicePolicy.load_state_dict` hands the updated weights to
+the kernel by a device-side repack (k_policy_pack).  `DevicePolicy.ppo_grad` is one PPO minibatch of
+SB3's `PPO.train` on the device (include/pgtg.h pgtg_ppo_grad: k_ppo_loss, k_ppo_dw1, k_ppo_reduce): the loss,
+its statistics and the gradient of all twelve tensors from the rollout's int8 rows, written into the module's
+`.grad` tensors; `Rollout.update` is the loop around it, with torch's norm clip and optimiser.
 
     policy = DevicePolicy(env)
-    policy.load_state_dict(module.state_dict())         # after every PPO update
+    policy.load_state_dict(module.state_dict())
     ro.collect(policy)
+    ro.update(policy, module, optimizer)                # n_epochs x minibatches; repacks after every step
 
-`policy_reference` restates the whole function in numpy at a chosen precision and `policy_uniform` the
-kernel's counter-based uniform draw (SB3 is not a dependency; the restatements are the tests' yardstick,
+`policy_reference` restates the whole function in numpy at a chosen precision, `ppo_reference` the PPO loss
+and its hand-derived gradient, and `policy_uniform` the kernel's counter-based uniform draw (SB3 is not a dependency; the restatements are the tests' yardstick,
 as gae_reference is).
 """
 from __future__ import annotations
@@ -117,6 +121,85 @@ def _host(t):
     return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t
 
 
+STAT_NAMES = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction")
+
+
+def ppo_terms(state_dict, obs_int8, actions, old_log_probs, advantages, returns, clip_range, ent_coef, vf_coef,
+              normalize, dtype=np.float64) -> dict:
+    """Every intermediate of one PPO minibatch at precision dtype (ppo_reference's working; the tests take the
+    accumulated magnitudes from it): the layers' inputs `x, h1p, h2p, h1v, h2v`, the derivatives of the loss
+    with respect to the layers' pre-activations `dz1p, dz2p, dlogits, dz1v, dz2v, dvalue` (already divided
+    by B), and the per-sample terms of the statistics `t_policy, t_value, t_entropy, ratio, log_ratio, clipped`."""
+    x = np.asarray(obs_int8)
+    if x.dtype != np.int8 or x.ndim != 2:
+        raise ValueError("obs_int8: an int8 [B, D] array")
+    w = {f: np.asarray(_host(state_dict[key]), dtype=dtype) for f, (key, _) in WEIGHT_KEYS.items()}
+    x = x.astype(dtype)
+    B = len(x)
+    act = np.asarray(_host(actions)).astype(np.int64)
+    old = np.asarray(_host(old_log_probs), dtype=dtype)
+    adv = np.asarray(_host(advantages), dtype=dtype)
+    ret = np.asarray(_host(returns), dtype=dtype)
+    if normalize and B > 1:  # (SB3: the unbiased std; skipped for a batch of one)
+        adv = (adv - adv.mean(dtype=dtype)) / (adv.std(ddof=1, dtype=dtype) + dtype(1e-8))
+    c, ec, vc = dtype(clip_range), dtype(ent_coef), dtype(vf_coef)
+    h1p = np.tanh(x @ w["w1p"].T + w["b1p"])
+    h2p = np.tanh(h1p @ w["w2p"].T + w["b2p"])
+    h1v = np.tanh(x @ w["w1v"].T + w["b1v"])
+    h2v = np.tanh(h1v @ w["w2v"].T + w["b2v"])
+    logits = h2p @ w["wa"].T + w["ba"]
+    value = (h2v @ w["wv"].T + w["bv"])[:, 0]
+    mx = logits.max(axis=1, keepdims=True)
+    lsm = logits - (mx + np.log(np.exp(logits - mx).sum(axis=1, keepdims=True, dtype=dtype)))
+    p = np.exp(lsm)
+    ar = np.arange(B)
+    log_ratio = lsm[ar, act] - old
+    ratio = np.exp(log_ratio)
+    p1, p2 = adv * ratio, adv * np.clip(ratio, 1 - c, 1 + c)
+    entropy = -(p * lsm).sum(axis=1, dtype=dtype)
+    through = (p1 < p2) | ((ratio >= 1 - c) & (ratio <= 1 + c))
+    g_logp = np.where(through, -adv * ratio, 0).astype(dtype)
+    onehot = np.zeros_like(p)
+    onehot[ar, act] = 1
+    dlogits = (g_logp[:, None] * (onehot - p) + ec * (p * (lsm + entropy[:, None]))) / dtype(B)
+    dvalue = vc * (-2 * (ret - value)) / dtype(B)
+    dz2p = (dlogits @ w["wa"]) * (1 - h2p * h2p)
+    dz1p = (dz2p @ w["w2p"]) * (1 - h1p * h1p)
+    dz2v = (dvalue[:, None] * w["wv"]) * (1 - h2v * h2v)
+    dz1v = (dz2v @ w["w2v"]) * (1 - h1v * h1v)
+    return dict(x=x, h1p=h1p, h2p=h2p, h1v=h1v, h2v=h2v, dz1p=dz1p, dz2p=dz2p, dlogits=dlogits, dz1v=dz1v, dz2v=dz2v,
+                dvalue=dvalue, t_policy=-np.minimum(p1, p2), t_value=(ret - value) ** 2, t_entropy=-entropy, ratio=ratio,
+                log_ratio=log_ratio, clipped=(np.abs(ratio - 1) > c).astype(dtype), p=p, lsm=lsm, adv=adv)
+
+
+# state-dict key of a layer's weight -> (its pre-activation derivative, its input) in ppo_terms
+PPO_LAYERS = {
+    "mlp_extractor.policy_net.0": ("dz1p", "x"), "mlp_extractor.policy_net.2": ("dz2p", "h1p"), "action_net": ("dlogits", "h2p"),
+    "mlp_extractor.value_net.0": ("dz1v", "x"), "mlp_extractor.value_net.2": ("dz2v", "h1v"), "value_net": ("dvalue", "h2v"),
+}
+
+
+def ppo_reference(state_dict, obs_int8, actions, old_log_probs, advantages, returns, clip_range, ent_coef, vf_coef,
+                  normalize, dtype=np.float64):
+    """SB3's PPO.train loss of one minibatch (defaults, clip_range_vf = None) and its gradient, derived by
+    hand, in numpy at precision dtype: obs_int8 [B, D], actions, old_log_probs, advantages, returns [B].
+    Returns (grads {state-dict key: array in nn.Linear layout}, stats [8]: STAT_NAMES then two zeros).  The
+    min passes the advantage where its unclipped branch is the smaller or the ratio lies inside the clip
+    interval, which is autograd's result off the clip edges."""
+    t = ppo_terms(state_dict, obs_int8, actions, old_log_probs, advantages, returns, clip_range, ent_coef, vf_coef,
+                  normalize, dtype)
+    grads = {}
+    for layer, (dz, inp) in PPO_LAYERS.items():
+        d = t[dz] if t[dz].ndim == 2 else t[dz][:, None]
+        grads[layer + ".weight"] = d.T @ t[inp]
+        grads[layer + ".bias"] = d.sum(axis=0, dtype=dtype)
+    m = lambda v: v.mean(dtype=dtype)  # noqa: E731
+    pol, val, ent = m(t["t_policy"]), m(t["t_value"]), m(t["t_entropy"])
+    stats = np.array([pol + dtype(ent_coef) * ent + dtype(vf_coef) * val, pol, val, ent,
+                      m((t["ratio"] - 1) - t["log_ratio"]), m(t["clipped"]), 0, 0], dtype=dtype)
+    return grads, stats
+
+
 class _MlpExtractor(nn.Module):
     def __init__(self, obs_dim: int):
         super().__init__()
@@ -170,6 +253,9 @@ class DevicePolicy:
             raise ValueError(f"pgtg_policy_packed_bytes({D}) failed ({rc})")
         self._packed = torch.zeros(nbytes.value // 4, dtype=torch.float32, device=self.device)
         self._loaded = False
+        self._grads = None      # ppo_grad's own gradient tensors
+        self._ppo_ws = None     # the largest workspace a ppo_grad has needed so far
+        self._ppo_keep = None   # what the last ppo_grad launch reads
 
     def _fail(self, rc: int) -> None:
         from .vector import _check
@@ -240,3 +326,66 @@ class DevicePolicy:
         out = self._out(out, obs.shape[0], torch.float32, "out")
         self._launch(obs, VALUE_ONLY, None, out, None, None, 0)
         return out
+
+    def ppo_grad(self, rollout, indices, grads=None, clip_range: float = 0.2, ent_coef: float = 0.0,
+                 vf_coef: float = 0.5, normalize_advantage: bool = True):
+        """One PPO minibatch on the samples `indices` (int64 [B] device tensor of flat sample indices,
+        rollout.sample_index's order; repeats allowed) of a finished int8 rollout: SB3's loss and its gradient
+        with respect to the twelve tensors, by pgtg_ppo_grad (three launches; the [B, D] batch is never
+        built).  Returns (grads, stats): grads {state-dict key: float32 device tensor}, overwritten -- the
+        policy's own set, allocated once, or the dict given, e.g. a module's .grad tensors; stats the device
+        tensor of eight floats (STAT_NAMES, two zeros).  The advantages' mean and 1 / (std + 1e-8) are two
+        small torch reductions on the env's stream (skipped for B <= 1, as in SB3); nothing synchronises.
+        An index outside the rollout is skipped by the kernel and counted (env.error_count()); in the mean and
+        the std of the advantages it stands as an advantage of 0, so that no mask has to reach the host."""
+        if not self._loaded:
+            raise ValueError("load_state_dict() first")
+        ro = rollout
+        if ro.env is not self.env or ro.obs_dim != self.obs_dim:
+            raise ValueError("the rollout is of another env or obs_dim")
+        if ro._dtype_code != 1:
+            raise ValueError("ppo_grad reads int8 rows: build the rollout with obs_dtype=torch.int8")
+        if not ro._finished:
+            raise ValueError("the rollout is not finished: collect() or finish() first")
+        idx = torch.as_tensor(indices, device=self.device).to(torch.int64).reshape(-1).contiguous()
+        B, D, T, N = idx.numel(), self.obs_dim, ro.n_steps, ro.num_envs
+        shapes = weight_shapes(D)
+        if grads is None:
+            if self._grads is None:
+                self._grads = {k: torch.zeros(s, dtype=torch.float32, device=self.device) for k, s in shapes.items()}
+            grads = self._grads
+        raw = _abi.PgtgPpoGrads()
+        for field, (key, _) in WEIGHT_KEYS.items():
+            g = grads.get(key)
+            if g is None or g.dtype != torch.float32 or tuple(g.shape) != shapes[key] or not g.is_contiguous() \
+                    or g.device != self.device:
+                raise ValueError(f"grads[{key!r}]: a contiguous float32 tensor of shape {shapes[key]} on {self.device}")
+            setattr(raw, field, g.data_ptr())
+        stats = torch.zeros(8, dtype=torch.float32, device=self.device)
+        if B == 0:
+            return grads, stats
+        nbytes = C.c_uint64()
+        rc = self.env._lib.pgtg_ppo_workspace_bytes(D, B, C.byref(nbytes))
+        if rc != _abi.PGTG_OK:
+            raise ValueError(f"pgtg_ppo_workspace_bytes({D}, {B}) failed ({rc})")
+        ws = self._ppo_ws  # (one buffer, grown to the largest batch seen: its contents do not matter)
+        if ws is None or ws.numel() * 4 < nbytes.value:
+            ws = self._ppo_ws = torch.empty(max(4, nbytes.value // 4), dtype=torch.float32, device=self.device)
+        adv_stats = None
+        if normalize_advantage and B > 1:
+            e, t = idx // T, idx % T
+            inside = (idx >= 0) & (idx < T * N)
+            adv = ro.advantages[t.clamp(0, T - 1), e.clamp(0, N - 1)] * inside  # (a skipped sample counts as 0)
+            adv_stats = torch.stack((adv.mean(), 1.0 / (adv.std() + 1e-8)))
+        p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+        a = _abi.PgtgPpoGrad(batch=B, obs_dim=D, steps=T, n=N, obs_pitch=ro.obs.stride(0), obs=p(ro.obs),
+                             indices=p(idx), actions=p(ro.actions), log_probs=p(ro.log_probs),
+                             advantages=p(ro.advantages), returns=p(ro.returns), packed=p(self._packed),
+                             adv_stats=p(adv_stats), clip_range=float(clip_range), ent_coef=float(ent_coef),
+                             vf_coef=float(vf_coef), workspace=p(ws), grads=raw, stats=p(stats))
+        self._ppo_keep = (idx, adv_stats, stats, grads)
+        self.env._bind_stream()
+        rc = self.env._lib.pgtg_ppo_grad(self.env._h, C.byref(a))
+        if rc != _abi.PGTG_OK:
+            self._fail(rc)
+        return grads, stats

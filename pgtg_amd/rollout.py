@@ -22,7 +22,8 @@ which reads obs[t] and writes the action, value and log-probability rows) the lo
 
     policy = DevicePolicy(env); policy.load_state_dict(module.state_dict())
     ro.collect(policy)                                           # T x (k_policy, the tick, V(terminal_obs)), k_gae
-    for obs_b, act_b, val_b, logp_b, adv_b, ret_b in ro.get(batch_size=4096): ...
+    ro.update(policy, module, optimizer)                         # SB3's PPO.train: per minibatch k_ppo_loss, k_ppo_dw1,
+                                                                 # k_ppo_reduce into module's .grad, then clip, step, repack
 
 While a Rollout records, it owns the handle's flat bindings (set_flat_outputs / set_flat_scalars): bind
 nothing else to them until `close()`.
@@ -271,6 +272,39 @@ class Rollout:
             e, t = sample_index(idx[lo:lo + bs], T)
             yield (self.obs[t, e].to(torch.float32), self.actions[t, e].to(torch.int64), self.values[t, e],
                    self.log_probs[t, e], self.advantages[t, e], self.returns[t, e])
+
+    # -- the PPO update ---------------------------------------------------------------------------
+    def update(self, policy, module, optimizer, n_epochs: int = 10, batch_size: int = 64, clip_range: float = 0.2,
+               ent_coef: float = 0.0, vf_coef: float = 0.5, max_grad_norm: float = 0.5,
+               normalize_advantage: bool = True, generator=None) -> list:
+        """SB3's PPO.train loop over the finished rollout with the library's gradient: per epoch one
+        torch.randperm(T * N) on the device (from `generator` if given), per minibatch of batch_size samples
+        policy.ppo_grad (k_ppo_loss, k_ppo_dw1, k_ppo_reduce on the int8 rows) straight into the .grad tensors
+        of `module` (an MlpPolicyReference on the env's device whose weights `policy` holds), then torch's
+        clip_grad_norm_, optimizer.step() and policy.load_state_dict(module.state_dict()).  Returns the
+        per-minibatch stats tensors (policy.STAT_NAMES), still on the device; nothing synchronises."""
+        import torch
+        if not self._finished:
+            raise ValueError("the rollout is not finished: collect() or finish() first")
+        if int(batch_size) < 1 or int(n_epochs) < 0:
+            raise ValueError("batch_size must be at least 1 and n_epochs at least 0")
+        params = dict(module.named_parameters())
+        grads = {}
+        for key, p in params.items():
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+            grads[key] = p.grad
+        total, out = self.n_steps * self.num_envs, []
+        for _ in range(int(n_epochs)):
+            perm = torch.randperm(total, device=self.device, generator=generator)
+            for lo in range(0, total, int(batch_size)):
+                _, stats = policy.ppo_grad(self, perm[lo:lo + int(batch_size)], grads=grads, clip_range=clip_range,
+                                           ent_coef=ent_coef, vf_coef=vf_coef, normalize_advantage=normalize_advantage)
+                torch.nn.utils.clip_grad_norm_(params.values(), max_grad_norm)
+                optimizer.step()
+                policy.load_state_dict(module.state_dict())
+                out.append(stats)
+        return out
 
     def close(self) -> None:
         """Unbind the flat rows and scalars from the handle (the tensors stay valid)."""
