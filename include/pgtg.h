@@ -441,6 +441,50 @@ typedef struct {
 } PgtgPpoGrad;
 int pgtg_ppo_workspace_bytes(uint64_t obs_dim, uint64_t batch, uint64_t* bytes);
 int pgtg_ppo_grad(pgtg_handle* h, const PgtgPpoGrad* a);
+/* The optimiser step that follows pgtg_ppo_grad (new; no reference function: it replaces
+ * torch.nn.utils.clip_grad_norm_, torch.optim.Adam.step with weight_decay = 0, amsgrad = False, maximize =
+ * False, and the repack of pgtg_policy_pack).  Over all twelve tensors, float32:
+ *   total = sqrt(sum g^2)        coef = min(1, max_grad_norm / (total + 1e-6))        g <- coef g  (not stored)
+ *   m <- m + (1 - beta1) (g - m)        v <- beta2 v + (1 - beta2) g^2
+ *   p <- p - (lr / (1 - beta1^step)) m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * with lr / (1 - beta1^step) and sqrt(1 - beta2^step) computed in double on the host and rounded once, as torch
+ * computes them in Python floats; lr, beta1 and beta2 enter those as the shortest decimals that round to the
+ * float32 given (0.999f stands for 0.999), so that 1 - beta2 is torch's.  params, exp_avg and exp_avg_sq are updated in place in SB3's nn.Linear
+ * layouts, grads is only read, and every word of packed (pgtg_policy_packed_bytes) is rewritten with the new
+ * weights in k_policy's layout, its padding words with 0: the bits pgtg_policy_pack would write from the new
+ * params.  grad_norm (device, optional) receives total.  Two launches (k_ppo_gnorm, k_ppo_adam), asynchronous on
+ * the handle's stream, no atomics: the partition is a function of obs_dim alone and every sum runs in a fixed
+ * order, so the same call from the same state gives the same bits.  workspace: pgtg_ppo_step_workspace_bytes
+ * bytes, 8-byte aligned, contents irrelevant (the sums of squares are taken in double).  Non-finite gradients are not detected: the result is what the arithmetic above
+ * gives (clip_grad_norm_ with error_if_nonfinite = False).  Any of the 48 tensor pointers, packed or workspace
+ * NULL, packed not 16-byte or workspace not 8-byte aligned, obs_dim outside [1, PGTG_POLICY_MAX_OBS_DIM], step == 0, a non-finite lr,
+ * eps or beta, a beta outside [0, 1), max_grad_norm NaN or <= 0 (+inf: no clip): PGTG_E_INVALID with a
+ * message, nothing is launched. */
+typedef struct {
+  const float *w1p, *b1p, *w2p, *b2p, *wa, *ba;
+  const float *w1v, *b1v, *w2v, *b2v, *wv, *bv;
+} PgtgPpoConstGrads;                 /* PgtgPpoGrads, read only */
+typedef struct {
+  uint64_t obs_dim;
+  PgtgPpoGrads params;               /* twelve float32 tensors, nn.Linear layout, updated in place */
+  PgtgPpoConstGrads grads;           /* read only (pgtg_ppo_grad's output) */
+  PgtgPpoGrads exp_avg, exp_avg_sq;  /* Adam's moments, same shapes, updated in place */
+  void* packed;                      /* pgtg_policy_pack's buffer: every word rewritten */
+  void* workspace;                   /* pgtg_ppo_step_workspace_bytes(obs_dim) bytes */
+  uint64_t step;                     /* 1 for the first step */
+  float lr, beta1, beta2, eps, max_grad_norm;   /* max_grad_norm = +inf: no clip */
+  float* grad_norm;                  /* optional: the total norm before clipping */
+} PgtgPpoStep;
+int pgtg_ppo_step_workspace_bytes(uint64_t obs_dim, uint64_t* bytes);
+int pgtg_ppo_step(pgtg_handle* h, const PgtgPpoStep* a);
+/* out = {mean, 1 / (std + 1e-8)} (device, float32) of the batch advantages[indices[s] % steps][indices[s] / steps],
+ * s = 0 .. batch-1: pgtg_ppo_grad's adv_stats.  The unbiased std in two passes (the mean, then the squared
+ * deviations); an index outside [0, steps * n) stands as an advantage of 0 (pgtg_ppo_grad still skips and counts
+ * that sample).  One launch of one workgroup (k_ppo_adv_stats), asynchronous on the handle's stream; the
+ * partition is a function of batch alone and the order is fixed.  A NULL pointer, batch < 2 (SB3 does not
+ * normalise a batch of one), steps or n of 0, steps * n overflowing: PGTG_E_INVALID, nothing is launched. */
+int pgtg_ppo_adv_stats(pgtg_handle* h, const void* advantages, const void* indices, uint64_t batch, uint64_t steps,
+                       uint64_t n, float* out);
 /* Re-emit the observation of every env into the bound outputs (after set_agent/add_car). */
 int pgtg_observe(pgtg_handle* h);
 /* Per-env uint64 digest of the car list into out_dev[N] (device; parity tests: the car term of

@@ -18,7 +18,7 @@ def __getattr__(name):
     if name == "Rollout":
         from .rollout import Rollout
         return Rollout
-    if name in ("DevicePolicy", "MlpPolicyReference"):  # (SB3's MlpPolicy: the kernel k_policy and its yardstick)
+    if name in ("DevicePolicy", "MlpPolicyReference", "DeviceAdam"):  # (SB3's MlpPolicy: k_policy, its yardstick, the optimiser step)
         from . import policy
         return getattr(policy, name)
     if name == "PGTGEnv":

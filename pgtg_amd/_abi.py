@@ -36,6 +36,7 @@ EXPORTED = [
     "pgtg_set_episode_stats", "pgtg_episode_summary", "pgtg_gae", "pgtg_flatten",
     "pgtg_policy", "pgtg_policy_pack", "pgtg_policy_packed_bytes", "pgtg_policy_chunk",
     "pgtg_ppo_workspace_bytes", "pgtg_ppo_grad",
+    "pgtg_ppo_step_workspace_bytes", "pgtg_ppo_step", "pgtg_ppo_adv_stats",
     "pgtg_snapshot_create", "pgtg_snapshot_destroy", "pgtg_snapshot_bytes", "pgtg_snapshot_save", "pgtg_snapshot_load",
 ]
 
@@ -130,6 +131,13 @@ class PgtgPpoGrad(C.Structure):
         ("grads", PgtgPpoGrads), ("stats", C.c_void_p)]
 
 
+class PgtgPpoStep(C.Structure):
+    _fields_ = [("obs_dim", C.c_uint64), ("params", PgtgPpoGrads), ("grads", PgtgPpoGrads), ("exp_avg", PgtgPpoGrads),
+                ("exp_avg_sq", PgtgPpoGrads), ("packed", C.c_void_p), ("workspace", C.c_void_p), ("step", C.c_uint64),
+                ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("max_grad_norm", C.c_float), ("grad_norm", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -186,6 +194,9 @@ def lib():
         "pgtg_policy_chunk": ([], C.c_int),
         "pgtg_ppo_workspace_bytes": ([u64, u64, C.POINTER(u64)], C.c_int),
         "pgtg_ppo_grad": ([vp, C.POINTER(PgtgPpoGrad)], C.c_int),
+        "pgtg_ppo_step_workspace_bytes": ([u64, C.POINTER(u64)], C.c_int),
+        "pgtg_ppo_step": ([vp, C.POINTER(PgtgPpoStep)], C.c_int),
+        "pgtg_ppo_adv_stats": ([vp, vp, vp, u64, u64, u64, vp], C.c_int),
         "pgtg_snapshot_create": ([vp, u64, C.POINTER(vp)], C.c_int),
         "pgtg_snapshot_destroy": ([vp], C.c_int),
         "pgtg_snapshot_bytes": ([vp, C.POINTER(u64), C.POINTER(u64)], C.c_int),

@@ -10,7 +10,7 @@ SRC = os.path.join(PKG, "csrc", "pgtg_env.hip")
 DEPS = [SRC, os.path.join(PKG, "csrc", "pgtg_device.h"), os.path.join(PKG, "csrc", "pgtg_tables.h"),
         os.path.join(PKG, "csrc", "pgtg_episode.h"), os.path.join(PKG, "csrc", "pgtg_snapshot.h"),
         os.path.join(PKG, "csrc", "pgtg_rollout.h"), os.path.join(PKG, "csrc", "pgtg_policy.h"),
-        os.path.join(PKG, "csrc", "pgtg_ppo.h"),
+        os.path.join(PKG, "csrc", "pgtg_ppo.h"), os.path.join(PKG, "csrc", "pgtg_ppo_step.h"),
         os.path.join(os.path.dirname(PKG), "include", "pgtg.h")]
 OUT = os.path.join(PKG, "libpgtg_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

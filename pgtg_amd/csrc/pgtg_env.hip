@@ -30,6 +30,7 @@
 #include "pgtg_rollout.h"
 #include "pgtg_policy.h"
 #include "pgtg_ppo.h"
+#include "pgtg_ppo_step.h"
 #include "pgtg_snapshot.h"
 
 namespace pgtg {
@@ -6575,6 +6576,94 @@ int pgtg_ppo_grad(pgtg_handle* h, const PgtgPpoGrad* a) {
   hipLaunchKernelGGL(k_ppo_loss, dim3((unsigned)pl.blocks), dim3(kPpoThreads), 0, h->stream, p);
   hipLaunchKernelGGL(k_ppo_dw1, dim3((unsigned)pl.dtiles, (unsigned)pl.segs), dim3(kPpoThreads), 0, h->stream, p);
   hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)rgrid), dim3(kPpoThreads), 0, h->stream, p);
+  HIPCHK(h, hipGetLastError());
+  return PGTG_OK;
+}
+
+// The optimiser step of a PPO minibatch and the advantage statistics (pgtg_ppo_step.h): the handle gives the
+// device, the stream and the error string
+int pgtg_ppo_step_workspace_bytes(uint64_t obs_dim, uint64_t* bytes) {
+  if (!bytes || obs_dim == 0 || obs_dim > kPolMaxObsDim) return PGTG_E_INVALID;
+  *bytes = (step_blocks(obs_dim) * sizeof(double) + 15) & ~(uint64_t)15;
+  return PGTG_OK;
+}
+
+// The double a caller rounded to the float x: its shortest decimal form that reads back as x (0.999f gives
+// 0.999, where the plain widening gives 0.99900001287 and 1 - beta2 would be off by 1.3e-5 of itself).
+static double widen_decimal(float x) {
+  if (!std::isfinite(x)) return x;
+  char buf[40];
+  for (int prec = 1; prec <= 9; prec++) {
+    snprintf(buf, sizeof buf, "%.*g", prec, (double)x);
+    const double d = strtod(buf, nullptr);
+    if ((float)d == x) return d;
+  }
+  return x;
+}
+
+int pgtg_ppo_step(pgtg_handle* h, const PgtgPpoStep* a) {
+  if (!h) return PGTG_E_INVALID;
+  if (!a) return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: no arguments");
+  if (a->obs_dim == 0 || a->obs_dim > kPolMaxObsDim)
+    return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: obs_dim outside [1, PGTG_POLICY_MAX_OBS_DIM]");
+  auto all12 = [](const auto& s) {
+    return s.w1p && s.b1p && s.w2p && s.b2p && s.wa && s.ba && s.w1v && s.b1v && s.w2v && s.b2v && s.wv && s.bv;
+  };
+  if (!all12(a->params) || !all12(a->grads) || !all12(a->exp_avg) || !all12(a->exp_avg_sq))
+    return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: all twelve pointers of params, grads, exp_avg and exp_avg_sq are required");
+  if (!a->packed || !a->workspace) return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: packed and workspace are required");
+  if ((uintptr_t)a->packed & 15u) return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: packed must be 16-byte aligned");
+  if ((uintptr_t)a->workspace & 7u) return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: workspace must be 8-byte aligned");
+  if (a->step == 0) return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: step counts from 1");
+  if (!std::isfinite(a->lr) || !std::isfinite(a->eps) || !std::isfinite(a->beta1) || !std::isfinite(a->beta2))
+    return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: lr, eps, beta1 and beta2 must be finite");
+  if (!(a->beta1 >= 0.f && a->beta1 < 1.f) || !(a->beta2 >= 0.f && a->beta2 < 1.f))
+    return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: beta1 and beta2 must be in [0, 1)");
+  if (!(a->max_grad_norm > 0.f))
+    return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: max_grad_norm must be above 0 (+inf: no clip)");
+  PpoStepArgs p;
+  auto put = [](auto& d, const auto& s) {
+    d.w1p = s.w1p, d.b1p = s.b1p, d.w2p = s.w2p, d.b2p = s.b2p, d.wa = s.wa, d.ba = s.ba;
+    d.w1v = s.w1v, d.b1v = s.b1v, d.w2v = s.w2v, d.b2v = s.b2v, d.wv = s.wv, d.bv = s.bv;
+  };
+  put(p.p, a->params);
+  put(p.g, a->grads);
+  put(p.m, a->exp_avg);
+  put(p.v, a->exp_avg_sq);
+  p.packed = (float*)a->packed;
+  p.ws = (double*)a->workspace;
+  p.grad_norm = a->grad_norm;
+  p.D = a->obs_dim;
+  // torch.optim.Adam's Python floats: the bias corrections and the step size in double, rounded once
+  // (lr and the betas as the decimals the caller wrote: torch holds them as Python floats)
+  const double b1 = widen_decimal(a->beta1), b2 = widen_decimal(a->beta2), st = (double)a->step;
+  p.step_size = (float)(widen_decimal(a->lr) / (1.0 - pow(b1, st)));
+  p.bc2_sqrt = (float)sqrt(1.0 - pow(b2, st));
+  p.w1 = (float)(1.0 - b1);
+  p.beta2 = a->beta2;
+  p.w2 = (float)(1.0 - b2);
+  p.eps = a->eps;
+  p.max_norm = a->max_grad_norm;
+  const uint64_t total = policy_layout(a->obs_dim).total;
+  const uint64_t grid = std::min<uint64_t>((total + kStepThreads - 1) / kStepThreads, kStepPackMaxBlocks);
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_ppo_gnorm, dim3((unsigned)step_blocks(a->obs_dim)), dim3(kStepThreads), 0, h->stream, p);
+  hipLaunchKernelGGL(k_ppo_adam, dim3((unsigned)grid), dim3(kStepThreads), 0, h->stream, p);
+  HIPCHK(h, hipGetLastError());
+  return PGTG_OK;
+}
+
+int pgtg_ppo_adv_stats(pgtg_handle* h, const void* advantages, const void* indices, uint64_t batch, uint64_t steps,
+                       uint64_t n, float* out) {
+  if (!h) return PGTG_E_INVALID;
+  if (!advantages || !indices || !out)
+    return fail(h, PGTG_E_INVALID, "pgtg_ppo_adv_stats: advantages, indices and out are required");
+  if (batch < 2) return fail(h, PGTG_E_INVALID, "pgtg_ppo_adv_stats: batch must be at least 2 (the unbiased std)");
+  if (steps == 0 || n == 0) return fail(h, PGTG_E_INVALID, "pgtg_ppo_adv_stats: steps and n must be at least 1");
+  if (steps > (UINT64_MAX >> 3) / n) return fail(h, PGTG_E_INVALID, "pgtg_ppo_adv_stats: steps * n overflows");
+  AdvStatsArgs p = {(const float*)advantages, (const int64_t*)indices, batch, steps, n, out};
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_ppo_adv_stats, dim3(1), dim3(kAdvThreads), 0, h->stream, p);
   HIPCHK(h, hipGetLastError());
   return PGTG_OK;
 }

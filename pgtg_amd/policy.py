@@ -10,15 +10,20 @@ real `policy.state_dict()` loads into it), and `DevicePolicy.load_state_dict` ha
 the kernel by a device-side repack (k_policy_pack).  `DevicePolicy.ppo_grad` is one PPO minibatch of
 SB3's `PPO.train` on the device (include/pgtg.h pgtg_ppo_grad: k_ppo_loss, k_ppo_dw1, k_ppo_reduce): the loss,
 its statistics and the gradient of all twelve tensors from the rollout's int8 rows, written into the module's
-`.grad` tensors; `Rollout.update` is the loop around it, with torch's norm clip and optimiser.
+`.grad` tensors; `Rollout.update` is the loop around it.  `DeviceAdam` is the optimiser step on the device
+(pgtg_ppo_step: k_ppo_gnorm, k_ppo_adam): the global-norm clip, Adam and the repack of the new weights for
+k_policy in two launches; with it (and `DevicePolicy.adv_stats`, k_ppo_adv_stats) a minibatch of
+`Rollout.update` is six launches of this library and nothing else.  With a torch optimiser the loop keeps
+torch's norm clip, `optimizer.step()` and a repack per minibatch.
 
     policy = DevicePolicy(env)
     policy.load_state_dict(module.state_dict())
+    opt = DeviceAdam(policy, module, lr=3e-4)           # or torch.optim.Adam(module.parameters(), ...)
     ro.collect(policy)
-    ro.update(policy, module, optimizer)                # n_epochs x minibatches; repacks after every step
+    ro.update(policy, module, opt)                      # n_epochs x minibatches
 
 `policy_reference` restates the whole function in numpy at a chosen precision, `ppo_reference` the PPO loss
-and its hand-derived gradient, and `policy_uniform` the kernel's counter-based uniform draw (SB3 is not a dependency; the restatements are the tests' yardstick,
+and its hand-derived gradient, `policy_adam_reference` the clip and Adam step, and `policy_uniform` the kernel's counter-based uniform draw (SB3 is not a dependency; the restatements are the tests' yardstick,
 as gae_reference is).
 """
 from __future__ import annotations
@@ -200,6 +205,32 @@ def ppo_reference(state_dict, obs_int8, actions, old_log_probs, advantages, retu
     return grads, stats
 
 
+def policy_adam_reference(params, grads, m, v, step, lr, betas, eps, max_grad_norm, dtype=np.float64):
+    """torch.nn.utils.clip_grad_norm_ followed by one torch.optim.Adam step (weight_decay = 0, amsgrad = False),
+    which is what pgtg_ppo_step computes, in numpy at precision dtype.  params, grads, m (exp_avg), v (exp_avg_sq):
+    {key: array or tensor} over the same keys; step counts from 1; max_grad_norm = inf: no clip.  Returns
+    (params, m, v, total_norm): new dicts, the inputs are not written.
+        total = sqrt(sum g^2)      g <- min(1, max_grad_norm / (total + 1e-6)) g
+        m <- m + (1 - beta1) (g - m)      v <- beta2 v + (1 - beta2) g^2
+        p <- p - (lr / (1 - beta1^step)) m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+    The bias corrections are Python floats (double), as in torch."""
+    if int(step) < 1:
+        raise ValueError("step counts from 1")
+    b1, b2 = (float(b) for b in betas)
+    cast = lambda d: {k: np.asarray(_host(x), dtype=dtype) for k, x in d.items()}  # noqa: E731
+    p, g, m, v = cast(params), cast(grads), cast(m), cast(v)
+    total = np.sqrt(sum((x * x).sum(dtype=dtype) for x in g.values()), dtype=dtype)
+    coef = min(dtype(1), dtype(max_grad_norm) / (total + dtype(1e-6)))
+    step_size = dtype(float(lr) / (1.0 - b1 ** int(step)))
+    bc2_sqrt = dtype(math.sqrt(1.0 - b2 ** int(step)))
+    for k in p:
+        gk = coef * g[k]
+        m[k] = m[k] + dtype(1.0 - b1) * (gk - m[k])
+        v[k] = dtype(b2) * v[k] + dtype(1.0 - b2) * gk * gk
+        p[k] = p[k] - step_size * m[k] / (np.sqrt(v[k]) / bc2_sqrt + dtype(eps))
+    return p, m, v, total
+
+
 class _MlpExtractor(nn.Module):
     def __init__(self, obs_dim: int):
         super().__init__()
@@ -328,7 +359,7 @@ class DevicePolicy:
         return out
 
     def ppo_grad(self, rollout, indices, grads=None, clip_range: float = 0.2, ent_coef: float = 0.0,
-                 vf_coef: float = 0.5, normalize_advantage: bool = True):
+                 vf_coef: float = 0.5, normalize_advantage: bool = True, adv_stats=None):
         """One PPO minibatch on the samples `indices` (int64 [B] device tensor of flat sample indices,
         rollout.sample_index's order; repeats allowed) of a finished int8 rollout: SB3's loss and its gradient
         with respect to the twelve tensors, by pgtg_ppo_grad (three launches; the [B, D] batch is never
@@ -337,7 +368,10 @@ class DevicePolicy:
         tensor of eight floats (STAT_NAMES, two zeros).  The advantages' mean and 1 / (std + 1e-8) are two
         small torch reductions on the env's stream (skipped for B <= 1, as in SB3); nothing synchronises.
         An index outside the rollout is skipped by the kernel and counted (env.error_count()); in the mean and
-        the std of the advantages it stands as an advantage of 0, so that no mask has to reach the host."""
+        the std of the advantages it stands as an advantage of 0, so that no mask has to reach the host.
+        adv_stats: a float32 [2] device tensor {mean, 1 / (std + 1e-8)} (self.adv_stats) to normalise with in
+        place of the torch reductions; the call then launches no torch kernel (the stats tensor is allocated
+        without a fill: k_ppo_reduce writes all eight)."""
         if not self._loaded:
             raise ValueError("load_state_dict() first")
         ro = rollout
@@ -361,7 +395,12 @@ class DevicePolicy:
                     or g.device != self.device:
                 raise ValueError(f"grads[{key!r}]: a contiguous float32 tensor of shape {shapes[key]} on {self.device}")
             setattr(raw, field, g.data_ptr())
-        stats = torch.zeros(8, dtype=torch.float32, device=self.device)
+        if adv_stats is not None:
+            adv_stats = self._out(adv_stats, 2, torch.float32, "adv_stats")
+        if adv_stats is not None and B > 0:
+            stats = torch.empty(8, dtype=torch.float32, device=self.device)
+        else:
+            stats = torch.zeros(8, dtype=torch.float32, device=self.device)
         if B == 0:
             return grads, stats
         nbytes = C.c_uint64()
@@ -371,8 +410,7 @@ class DevicePolicy:
         ws = self._ppo_ws  # (one buffer, grown to the largest batch seen: its contents do not matter)
         if ws is None or ws.numel() * 4 < nbytes.value:
             ws = self._ppo_ws = torch.empty(max(4, nbytes.value // 4), dtype=torch.float32, device=self.device)
-        adv_stats = None
-        if normalize_advantage and B > 1:
+        if adv_stats is None and normalize_advantage and B > 1:
             e, t = idx // T, idx % T
             inside = (idx >= 0) & (idx < T * N)
             adv = ro.advantages[t.clamp(0, T - 1), e.clamp(0, N - 1)] * inside  # (a skipped sample counts as 0)
@@ -389,3 +427,141 @@ class DevicePolicy:
         if rc != _abi.PGTG_OK:
             self._fail(rc)
         return grads, stats
+
+    def adv_stats(self, rollout, indices, out=None):
+        """{mean, 1 / (std + 1e-8)} of the advantages of the samples `indices` (as ppo_grad takes them; at least
+        two) into out or a fresh float32 [2] device tensor: one launch of k_ppo_adv_stats on the env's stream
+        (include/pgtg.h pgtg_ppo_adv_stats), for ppo_grad's adv_stats.  The unbiased std; an index outside the
+        rollout stands as an advantage of 0, as in ppo_grad's own reductions."""
+        ro = rollout
+        if ro.env is not self.env:
+            raise ValueError("the rollout is of another env")
+        if not ro._finished:
+            raise ValueError("the rollout is not finished: collect() or finish() first")
+        idx = torch.as_tensor(indices, device=self.device).to(torch.int64).reshape(-1).contiguous()
+        if idx.numel() < 2:
+            raise ValueError("adv_stats needs at least two samples (SB3 does not normalise a batch of one)")
+        out = self._out(out, 2, torch.float32, "out")
+        self._adv_keep = (idx, out)
+        self.env._bind_stream()
+        rc = self.env._lib.pgtg_ppo_adv_stats(self.env._h, C.c_void_p(ro.advantages.data_ptr()), C.c_void_p(idx.data_ptr()),
+                                              idx.numel(), ro.n_steps, ro.num_envs, C.c_void_p(out.data_ptr()))
+        if rc != _abi.PGTG_OK:
+            self._fail(rc)
+        return out
+
+
+class DeviceAdam:
+    """torch.nn.utils.clip_grad_norm_ + torch.optim.Adam (weight_decay 0, no amsgrad) + the repack for k_policy
+    as one call of pgtg_ppo_step (k_ppo_gnorm, k_ppo_adam: two launches on the env's stream, no torch kernel, no
+    host synchronisation).  module: an MlpPolicyReference on the policy's device whose parameters are contiguous
+    float32; they are updated in place, so module.state_dict() stays the truth, and the policy's packed buffer
+    is rewritten by the same launch (no policy.load_state_dict follows).  The moments and the step count live
+    here; `lr` is read at every step (a schedule is an assignment); `last_grad_norm` is the device tensor [1] of
+    the last step's total norm before clipping.  state_dict() / load_state_dict() speak torch.optim.Adam's format
+    over module.parameters()' order, so a run can move between the two optimisers."""
+
+    def __init__(self, policy: DevicePolicy, module, lr: float = 3e-4, betas=(0.9, 0.999), eps: float = 1e-5):
+        self.policy, self.module = policy, module
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.step_count = 0
+        named = dict(module.named_parameters())
+        shapes = weight_shapes(policy.obs_dim)
+        for key, shape in shapes.items():
+            p = named.get(key)
+            if p is None:
+                raise ValueError(f"the module has no parameter {key!r}")
+            if p.dtype != torch.float32 or tuple(p.shape) != shape or not p.is_contiguous() or p.device != policy.device:
+                raise ValueError(f"{key!r}: a contiguous float32 parameter of shape {shape} on {policy.device}")
+        self._keys = [k for k in named if k in shapes]  # module.parameters()' order
+        if len(self._keys) != len(named):
+            raise ValueError(f"the module has parameters beyond MlpPolicy's twelve: {sorted(set(named) - set(shapes))}")
+        self._params = {k: named[k] for k in self._keys}
+        self.exp_avg = {k: torch.zeros_like(p, requires_grad=False) for k, p in self._params.items()}
+        self.exp_avg_sq = {k: torch.zeros_like(p, requires_grad=False) for k, p in self._params.items()}
+        self.last_grad_norm = torch.zeros(1, dtype=torch.float32, device=policy.device)
+        nbytes = C.c_uint64()
+        rc = policy.env._lib.pgtg_ppo_step_workspace_bytes(policy.obs_dim, C.byref(nbytes))
+        if rc != _abi.PGTG_OK:
+            raise ValueError(f"pgtg_ppo_step_workspace_bytes({policy.obs_dim}) failed ({rc})")
+        self._ws = torch.empty(nbytes.value // 4, dtype=torch.float32, device=policy.device)
+        self._raw = _abi.PgtgPpoStep(obs_dim=policy.obs_dim, packed=policy._packed.data_ptr(), workspace=self._ws.data_ptr(),
+                                     grad_norm=self.last_grad_norm.data_ptr())
+        for field, (key, _) in WEIGHT_KEYS.items():
+            setattr(self._raw.params, field, self._params[key].data_ptr())
+            setattr(self._raw.exp_avg, field, self.exp_avg[key].data_ptr())
+            setattr(self._raw.exp_avg_sq, field, self.exp_avg_sq[key].data_ptr())
+
+    def step(self, grads=None, max_grad_norm: float | None = 0.5) -> None:
+        """One optimiser step from grads {state-dict key: contiguous float32 device tensor} (default: the
+        module's .grad tensors; they are read, not written): the global norm over all twelve, the clip to
+        max_grad_norm (None or inf: none), Adam, and the policy's packed buffer rewritten."""
+        pol, shapes = self.policy, weight_shapes(self.policy.obs_dim)
+        raw = self._raw
+        for field, (key, _) in WEIGHT_KEYS.items():
+            p = self._params[key]
+            g = p.grad if grads is None else grads.get(key)
+            if g is None or g.dtype != torch.float32 or tuple(g.shape) != shapes[key] or not g.is_contiguous() \
+                    or g.device != pol.device:
+                raise ValueError(f"gradient of {key!r}: a contiguous float32 tensor of shape {shapes[key]} on {pol.device}")
+            if p.data_ptr() != getattr(raw.params, field):
+                raise ValueError(f"{key!r}: the module's parameter storage was replaced; build a new DeviceAdam")
+            setattr(raw.grads, field, g.data_ptr())
+        raw.step = self.step_count + 1
+        raw.lr, (raw.beta1, raw.beta2), raw.eps = float(self.lr), self.betas, self.eps
+        raw.max_grad_norm = math.inf if max_grad_norm is None else float(max_grad_norm)
+        self._keep = grads
+        pol.env._bind_stream()
+        rc = pol.env._lib.pgtg_ppo_step(pol.env._h, C.byref(raw))
+        if rc != _abi.PGTG_OK:
+            pol._fail(rc)
+        self.step_count += 1
+        pol._loaded = True
+
+    def zero_grad(self, set_to_none: bool = False) -> None:
+        """Nothing to do for pgtg_ppo_grad, which overwrites; here for loops written for torch.optim."""
+        for p in self._params.values():
+            if p.grad is not None:
+                if set_to_none:
+                    p.grad = None
+                else:
+                    p.grad.zero_()
+
+    def state_dict(self) -> dict:
+        """torch.optim.Adam's state dict over module.parameters()' order (clones; `step` a host int)."""
+        state = {}
+        if self.step_count:
+            state = {i: {"step": int(self.step_count), "exp_avg": self.exp_avg[k].clone(), "exp_avg_sq": self.exp_avg_sq[k].clone()}
+                     for i, k in enumerate(self._keys)}
+        group = dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=0, amsgrad=False, maximize=False, foreach=None,
+                     capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False,
+                     params=list(range(len(self._keys))))
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd) -> None:
+        """Take a torch.optim.Adam (or DeviceAdam) state dict over the same parameters: lr, betas, eps, the
+        moments (copied into this optimiser's own tensors) and the step count (an int or a tensor; one count
+        for all parameters).  ValueError for another shape of state, weight decay or amsgrad."""
+        groups = sd["param_groups"]
+        if len(groups) != 1 or list(groups[0]["params"]) != list(range(len(self._keys))):
+            raise ValueError(f"one parameter group over {len(self._keys)} parameters is expected")
+        g = groups[0]
+        if g.get("weight_decay", 0) or g.get("amsgrad", False) or g.get("maximize", False):
+            raise ValueError("weight_decay, amsgrad and maximize are not supported")
+        state = sd["state"]
+        if state and sorted(state) != list(range(len(self._keys))):
+            raise ValueError("the state must hold every parameter or none")
+        steps = {int(float(s["step"])) for s in state.values()}
+        if len(steps) > 1:
+            raise ValueError(f"one step count for all parameters is expected, got {sorted(steps)}")
+        for i, k in enumerate(self._keys):
+            for mine, name in ((self.exp_avg, "exp_avg"), (self.exp_avg_sq, "exp_avg_sq")):
+                if state:
+                    t = torch.as_tensor(state[i][name])
+                    if tuple(t.shape) != tuple(mine[k].shape):
+                        raise ValueError(f"{name} of parameter {i} ({k}) has shape {tuple(t.shape)}")
+                    mine[k].copy_(t)
+                else:
+                    mine[k].zero_()
+        self.lr, self.betas, self.eps = float(g["lr"]), (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"])
+        self.step_count = steps.pop() if steps else 0

@@ -282,8 +282,13 @@ class Rollout:
         policy.ppo_grad (k_ppo_loss, k_ppo_dw1, k_ppo_reduce on the int8 rows) straight into the .grad tensors
         of `module` (an MlpPolicyReference on the env's device whose weights `policy` holds), then torch's
         clip_grad_norm_, optimizer.step() and policy.load_state_dict(module.state_dict()).  Returns the
-        per-minibatch stats tensors (policy.STAT_NAMES), still on the device; nothing synchronises."""
+        per-minibatch stats tensors (policy.STAT_NAMES), still on the device; nothing synchronises.
+        With a policy.DeviceAdam over (policy, module) as the optimizer a minibatch is this library's launches
+        alone: policy.adv_stats (k_ppo_adv_stats; when normalising more than one sample), policy.ppo_grad with
+        those statistics, and optimizer.step(max_grad_norm=...) (k_ppo_gnorm, k_ppo_adam: clip, Adam and the
+        repack) -- no torch kernel but the epoch's randperm, no clip_grad_norm_ and no load_state_dict."""
         import torch
+        from .policy import DeviceAdam
         if not self._finished:
             raise ValueError("the rollout is not finished: collect() or finish() first")
         if int(batch_size) < 1 or int(n_epochs) < 0:
@@ -295,6 +300,19 @@ class Rollout:
                 p.grad = torch.zeros_like(p)
             grads[key] = p.grad
         total, out = self.n_steps * self.num_envs, []
+        if isinstance(optimizer, DeviceAdam):
+            if optimizer.policy is not policy or optimizer.module is not module:
+                raise ValueError("the DeviceAdam was built over another policy or module")
+            for _ in range(int(n_epochs)):
+                perm = torch.randperm(total, device=self.device, generator=generator)
+                for lo in range(0, total, int(batch_size)):
+                    idx = perm[lo:lo + int(batch_size)]
+                    st = policy.adv_stats(self, idx) if normalize_advantage and idx.numel() > 1 else None
+                    _, stats = policy.ppo_grad(self, idx, grads=grads, clip_range=clip_range, ent_coef=ent_coef,
+                                               vf_coef=vf_coef, normalize_advantage=normalize_advantage, adv_stats=st)
+                    optimizer.step(grads=grads, max_grad_norm=max_grad_norm)
+                    out.append(stats)
+            return out
         for _ in range(int(n_epochs)):
             perm = torch.randperm(total, device=self.device, generator=generator)
             for lo in range(0, total, int(batch_size)):
