@@ -17,15 +17,16 @@ if ROOT not in sys.path:
 from pgtg_amd.config import add_rule, make_spec  # noqa: E402
 
 
-def load_traj(name: str) -> dict:
-    z = np.load(os.path.join(GOLDEN, f"traj_{name}.npz"), allow_pickle=False)
+def load_traj(name: str, sub: str = "") -> dict:
+    """sub: a folder below tests/golden ("fuzz")"""
+    z = np.load(os.path.join(GOLDEN, sub, f"traj_{name}.npz"), allow_pickle=False)
     d = {k: z[k] for k in z.files}
     d["meta"] = json.loads(bytes(d["meta"]).decode())
     return d
 
 
-def traj_names() -> list[str]:
-    return sorted(f[5:-4] for f in os.listdir(GOLDEN) if f.startswith("traj_"))
+def traj_names(sub: str = "") -> list[str]:
+    return sorted(f[5:-4] for f in os.listdir(os.path.join(GOLDEN, sub)) if f.startswith("traj_"))
 
 
 def spec_for(meta: dict):
@@ -112,8 +113,15 @@ def has_traffic(meta: dict) -> bool:
     return float(meta["kwargs"].get("traffic_density", 0) or 0) > 0
 
 
-def replay_vec(d: dict, n_envs: int | None = None, steps: int | None = None) -> list[str]:
-    """Replay a golden trajectory through the HIP vector env (auto-reset); mismatch strings."""
+def replay_vec(d: dict, n_envs: int | None = None, steps: int | None = None, n_batch: int | None = None,
+               at=None, tune: dict | None = None, info: dict | None = None) -> list[str]:
+    """Replay a golden trajectory through the HIP vector env (auto-reset); mismatch strings.
+
+    n_batch, at: plant the fixture's envs in a batch of n_batch envs, env j at batch index at[j].  The
+    batch is reset with one seed per env: seed_base + j at at[j], a filler seed (fixed rng, far above
+    every fixture's seeds) everywhere else; the fillers step with fixed random actions.  Every
+    comparison is made at the planted indices.  tune: PGTGVecEnv's.  info (dict): gets "step_kernel"
+    and, after the last step, "errors" (error_count()[0])."""
     import torch
     from pgtg_amd.vector import PGTGVecEnv
     meta = d["meta"]
@@ -121,79 +129,102 @@ def replay_vec(d: dict, n_envs: int | None = None, steps: int | None = None) -> 
     perm = channel_perm(spec, meta["keys"])
     N = meta["N"] if n_envs is None else min(n_envs, meta["N"])
     T = meta["T"] if steps is None else min(steps, meta["T"])
-    env = PGTGVecEnv(N, spec=spec, autoreset=True)
+    planted = n_batch is not None or at is not None
+    ix = list(range(N)) if at is None else [int(b) for b in at][:N]
+    B = N if n_batch is None else int(n_batch)
+    assert len(ix) == N and len(set(ix)) == N and all(0 <= b < B for b in ix), (ix, N, B)
+    env = PGTGVecEnv(B, spec=spec, autoreset=True, tune=tune)
     bad: list[str] = []
-    obs, _ = env.reset(seed=meta["seed_base"])
-    torch.cuda.synchronize()
-    m = env.obs_map.cpu().numpy()[:, perm]
-    pos = env.position.cpu().numpy()
-    for i in range(N):
-        if has_traffic(meta) and digest(env.cars(i)) != int(d["init_cars_dig"][i]):
-            bad.append(f"env{i} reset cars")
-        if not np.array_equal(m[i], d["init_obs"][i]):
-            bad.append(f"env{i} reset obs")
-        if tuple(pos[i]) != tuple(d["init_pos"][i]):
-            bad.append(f"env{i} reset pos {pos[i]} vs {d['init_pos'][i]}")
-        if spec.next_subgoal and int(env.nsd[i]) != int(d["init_nsd"][i]):
-            bad.append(f"env{i} reset nsd")
-    reset_map = {(int(t), int(i)): k for k, (t, i) in enumerate(d["reset_idx"])}
-    for t in range(T):
-        acts = torch.as_tensor(d["actions"][t, :N].astype(np.uint8)).cuda()
-        env.step(acts)
+    try:
+        if info is not None:
+            info["step_kernel"] = env.step_kernel()
+        if planted:
+            rng = np.random.default_rng(0xF177)
+            seeds = (1_000_003 + rng.integers(0, 2**31, B)).tolist()
+            for j, b in enumerate(ix):
+                seeds[b] = meta["seed_base"] + j
+            filler = rng.integers(0, 9, (T, B)).astype(np.uint8)
+            obs, _ = env.reset(seed=seeds)
+        else:
+            obs, _ = env.reset(seed=meta["seed_base"])
         torch.cuda.synchronize()
-        m = env.obs_map.cpu().numpy()[:, perm]
-        fm = env.final_map.cpu().numpy()[:, perm]
-        pos, vel = env.position.cpu().numpy(), env.velocity.cpu().numpy()
-        fpos, fvel = env.final_position.cpu().numpy(), env.final_velocity.cpu().numpy()
-        rew, term = env.reward.cpu().numpy(), env.terminated.cpu().numpy()
-        trunc = env.truncated.cpu().numpy()
-        cost = env.cost.cpu().numpy() if env.cost is not None else np.zeros(N)
-        brk = env.braking.cpu().numpy()
-        nsd = env.nsd.cpu().numpy() if env.nsd is not None else None
-        fnsd = env.final_nsd.cpu().numpy() if env.final_nsd is not None else None
-        check_cars = has_traffic(meta)
-        for i in range(N):
-            tag = f"env{i} t{t}"
-            if check_cars:
-                dig = digest(env.cars(i))
-                want = d["reset_cars_dig"][reset_map[(t, i)]] if term[i] else d["cars_dig"][t, i]
-                if dig != int(want):
-                    bad.append(f"{tag} cars")
-            if bool(term[i]) != bool(d["terminated"][t, i]) or trunc[i]:
-                bad.append(f"{tag} terminated {term[i]} vs {d['terminated'][t, i]}")
-                continue
-            if bool(brk[i]) != bool(d["braking"][t, i]):
-                bad.append(f"{tag} braking {brk[i]} vs {d['braking'][t, i]}")
-            if "triggered" in d and int(brk[i]) != int(d["triggered"][t, i]):
-                bad.append(f"{tag} triggered rules {int(brk[i]):#04x} vs {int(d['triggered'][t, i]):#04x}")
-            if rew[i] != d["reward"][t, i] or cost[i] != d["cost"][t, i]:
-                bad.append(f"{tag} reward {rew[i]} vs {d['reward'][t, i]} cost {cost[i]} vs {d['cost'][t, i]}")
-            if term[i]:
-                if not np.array_equal(fm[i], d["obs"][t, i]):
-                    bad.append(f"{tag} final obs")
-                if tuple(fpos[i]) != tuple(d["pos"][t, i]) or tuple(fvel[i]) != tuple(d["vel"][t, i]):
-                    bad.append(f"{tag} final pos/vel")
-                if fnsd is not None and fnsd[i] != d["nsd"][t, i]:
-                    bad.append(f"{tag} final nsd")
-                k = reset_map[(t, i)]
-                if not np.array_equal(m[i], d["reset_obs"][k]):
-                    bad.append(f"{tag} autoreset obs")
-                if tuple(pos[i]) != tuple(d["reset_pos"][k]):
-                    bad.append(f"{tag} autoreset pos")
-                if nsd is not None and nsd[i] != d["reset_nsd"][k]:
-                    bad.append(f"{tag} autoreset nsd")
+        m = env.obs_map.cpu().numpy()[ix][:, perm]
+        pos = env.position.cpu().numpy()[ix]
+        nsd = env.nsd.cpu().numpy()[ix] if env.nsd is not None else None
+        for i, b in enumerate(ix):
+            tag = f"env{i}@{b}" if planted else f"env{i}"
+            if has_traffic(meta) and digest(env.cars(b)) != int(d["init_cars_dig"][i]):
+                bad.append(f"{tag} reset cars")
+            if not np.array_equal(m[i], d["init_obs"][i]):
+                bad.append(f"{tag} reset obs")
+            if tuple(pos[i]) != tuple(d["init_pos"][i]):
+                bad.append(f"{tag} reset pos {pos[i]} vs {d['init_pos'][i]}")
+            if spec.next_subgoal and int(nsd[i]) != int(d["init_nsd"][i]):
+                bad.append(f"{tag} reset nsd")
+        reset_map = {(int(t), int(i)): k for k, (t, i) in enumerate(d["reset_idx"])}
+        for t in range(T):
+            if planted:
+                a = filler[t].copy()
+                a[ix] = d["actions"][t, :N]
             else:
-                if not np.array_equal(m[i], d["obs"][t, i]):
-                    diff = [meta["keys"][c] for c in range(len(perm)) if not np.array_equal(m[i, c], d["obs"][t, i, c])]
-                    bad.append(f"{tag} obs {diff}")
-                if tuple(pos[i]) != tuple(d["pos"][t, i]) or tuple(vel[i]) != tuple(d["vel"][t, i]):
-                    bad.append(f"{tag} pos/vel {pos[i]} {vel[i]} vs {d['pos'][t, i]} {d['vel'][t, i]}")
-                if nsd is not None and nsd[i] != d["nsd"][t, i]:
-                    bad.append(f"{tag} nsd {nsd[i]} vs {d['nsd'][t, i]}")
-            if len(bad) > 30:
-                env.close()
-                return bad
-    env.close()
+                a = d["actions"][t, :N].astype(np.uint8)
+            env.step(torch.as_tensor(a.astype(np.uint8)).cuda())
+            torch.cuda.synchronize()
+            m = env.obs_map.cpu().numpy()[ix][:, perm]
+            fm = env.final_map.cpu().numpy()[ix][:, perm]
+            pos, vel = env.position.cpu().numpy()[ix], env.velocity.cpu().numpy()[ix]
+            fpos, fvel = env.final_position.cpu().numpy()[ix], env.final_velocity.cpu().numpy()[ix]
+            rew, term = env.reward.cpu().numpy()[ix], env.terminated.cpu().numpy()[ix]
+            trunc = env.truncated.cpu().numpy()[ix]
+            cost = env.cost.cpu().numpy()[ix] if env.cost is not None else np.zeros(N)
+            brk = env.braking.cpu().numpy()[ix]
+            nsd = env.nsd.cpu().numpy()[ix] if env.nsd is not None else None
+            fnsd = env.final_nsd.cpu().numpy()[ix] if env.final_nsd is not None else None
+            check_cars = has_traffic(meta)
+            for i, b in enumerate(ix):
+                tag = f"env{i}@{b} t{t}" if planted else f"env{i} t{t}"
+                if check_cars:
+                    dig = digest(env.cars(b))
+                    want = d["reset_cars_dig"][reset_map[(t, i)]] if term[i] and (t, i) in reset_map else d["cars_dig"][t, i]
+                    if dig != int(want):
+                        bad.append(f"{tag} cars")
+                if bool(term[i]) != bool(d["terminated"][t, i]) or trunc[i]:
+                    bad.append(f"{tag} terminated {term[i]} vs {d['terminated'][t, i]}")
+                    continue
+                if bool(brk[i]) != bool(d["braking"][t, i]):
+                    bad.append(f"{tag} braking {brk[i]} vs {d['braking'][t, i]}")
+                if "triggered" in d and int(brk[i]) != int(d["triggered"][t, i]):
+                    bad.append(f"{tag} triggered rules {int(brk[i]):#04x} vs {int(d['triggered'][t, i]):#04x}")
+                if rew[i] != d["reward"][t, i] or cost[i] != d["cost"][t, i]:
+                    bad.append(f"{tag} reward {rew[i]} vs {d['reward'][t, i]} cost {cost[i]} vs {d['cost'][t, i]}")
+                if term[i]:
+                    if not np.array_equal(fm[i], d["obs"][t, i]):
+                        bad.append(f"{tag} final obs")
+                    if tuple(fpos[i]) != tuple(d["pos"][t, i]) or tuple(fvel[i]) != tuple(d["vel"][t, i]):
+                        bad.append(f"{tag} final pos/vel")
+                    if fnsd is not None and fnsd[i] != d["nsd"][t, i]:
+                        bad.append(f"{tag} final nsd")
+                    k = reset_map[(t, i)]
+                    if not np.array_equal(m[i], d["reset_obs"][k]):
+                        bad.append(f"{tag} autoreset obs")
+                    if tuple(pos[i]) != tuple(d["reset_pos"][k]):
+                        bad.append(f"{tag} autoreset pos")
+                    if nsd is not None and nsd[i] != d["reset_nsd"][k]:
+                        bad.append(f"{tag} autoreset nsd")
+                else:
+                    if not np.array_equal(m[i], d["obs"][t, i]):
+                        diff = [meta["keys"][c] for c in range(len(perm)) if not np.array_equal(m[i, c], d["obs"][t, i, c])]
+                        bad.append(f"{tag} obs {diff}")
+                    if tuple(pos[i]) != tuple(d["pos"][t, i]) or tuple(vel[i]) != tuple(d["vel"][t, i]):
+                        bad.append(f"{tag} pos/vel {pos[i]} {vel[i]} vs {d['pos'][t, i]} {d['vel'][t, i]}")
+                    if nsd is not None and nsd[i] != d["nsd"][t, i]:
+                        bad.append(f"{tag} nsd {nsd[i]} vs {d['nsd'][t, i]}")
+                if len(bad) > 30:
+                    return bad
+        if info is not None:
+            info["errors"] = int(env.error_count()[0])
+    finally:
+        env.close()
     return bad
 
 

@@ -2,8 +2,11 @@
 in random order, sliding windows, next-subgoal direction, rewards and penalties, obstacle effect
 probabilities, traffic density, light phases, driver mix, cost channel) on maps of up to 64 tiles
 and batches of 64-3000 envs, every step compared with the CPU oracle on a sample of envs: observations, reward, cost,
-termination, position, next-subgoal direction and cars.  The oracle is pinned to the reference's
-fixtures (tests/test_oracle_golden.py); this widens the feature combinations the HIP path is held to."""
+termination, position, next-subgoal direction and cars.  The oracle is pinned to the reference on
+these very 40 configurations by the fuzz fixtures (tests/golden/fuzz/traj_fuzz_NN.npz is
+random_kwargs(NN) run by the reference; tests/test_oracle_fuzz.py) besides the hand-picked ones
+(tests/test_oracle_golden.py); this widens the feature combinations the HIP path is held to.  The
+distribution itself lives in tests/fuzz_configs.py, which the fixture generator imports too."""
 import warnings
 
 import numpy as np
@@ -11,52 +14,11 @@ import pytest
 import torch
 
 import helpers  # noqa: F401
+from fuzz_configs import FEATURES, random_kwargs  # noqa: F401
 from oracle.oracle import OracleEnv
 from pgtg_amd import config as cfg
 
 pytestmark = pytest.mark.gpu
-
-FEATURES = ["walls", "goals", "ice", "broken road", "sand", "traffic", "traffic_light", "start", "subgoal",
-            "used subgoal", "final goal", "car_spawner", "wall"]
-
-
-def random_kwargs(k: int) -> dict:
-    r = np.random.default_rng(1000 + k)
-    w, h = int(r.integers(2, 9)), int(r.integers(2, 9))  # up to 64 tiles
-    feats = list(r.choice(FEATURES, size=int(r.integers(1, 7)), replace=False))
-    feats += list(r.choice(cfg.LANES, size=int(r.integers(0, 3)), replace=False))
-    r.shuffle(feats)
-    prof = r.random(5) + 0.05
-    kw = dict(
-        random_map_width=w, random_map_height=h,
-        random_map_percentage_of_connections=float(r.choice([0.0, 0.3, 0.5, 0.8, 1.0])),
-        random_map_obstacle_probability=float(r.choice([0.0, 0.2, 0.6])),
-        random_map_ice_probability_weight=int(r.integers(0, 3)),
-        random_map_broken_road_probability_weight=int(r.integers(0, 3)),
-        random_map_sand_probability_weight=int(r.integers(0, 3)),
-        random_map_traffic_light_probability_weight=int(r.integers(1, 3)),
-        features_to_include_in_observation=[str(f) for f in feats],
-        use_sliding_observation_window=bool(r.random() < 0.4),
-        sliding_observation_window_size=int(r.integers(2, 6)),
-        use_next_subgoal_direction=bool(r.random() < 0.5),
-        sum_subgoals_reward=int(r.choice([0, 50, 100])),
-        final_goal_bonus=int(r.choice([0, 10])),
-        crash_penalty=int(r.choice([0, 100])),
-        traffic_light_violation_penalty=int(r.choice([0, 50])),
-        standing_still_penalty=float(r.choice([0.0, 0.5])),
-        already_visited_position_penalty=float(r.choice([0.0, 0.25])),
-        ice_probability=float(r.choice([0.0, 0.1, 0.5])),
-        street_damage_probability=float(r.choice([0.0, 0.1, 0.5])),
-        sand_probability=float(r.choice([0.0, 0.2, 0.6])),
-        traffic_density=float(r.choice([0.0, 0.0, 0.1, 0.3])) if w * h <= 30 else 0.0,
-        traffic_light_phases_duration=tuple(int(v) for v in r.integers(1, 8, size=3)),
-        ignore_traffic_collisions=bool(r.random() < 0.3),
-        separate_reward_cost=bool(r.random() < 0.5),
-    )
-    for name, p in zip(cfg.DRIVER_PROFILES, prof / prof.sum()):
-        kw[f"{name}_driver_percentage"] = float(p)
-    return kw
-
 
 @pytest.mark.parametrize("k", range(40))
 def test_random_config_parity(k):

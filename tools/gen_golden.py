@@ -12,7 +12,13 @@ rule_engine.rule_triggers) and the post-reset observation of envs that were rese
 A case of RULE_CASES carries its own traffic rules: after construction the env's default rules are
 removed and the case's are added through add_traffic_rule; the list is stored in the fixture's meta.
 
-Usage:  python tools/gen_golden.py [name ...]
+A case of FUZZ_CASES is a draw of tests/fuzz_configs.py (imported, not restated): fuzz_NN is
+random_kwargs(NN), the configuration tests/test_gpu_config_fuzz.py runs as case NN, wide_NN is
+wide_kwargs(NN).  They go to tests/golden/fuzz/ and are made on request only.
+
+Usage:  python tools/gen_golden.py [name | prefix* ...]
+        no argument: CONFIGS, RULE_CASES, the numpy vectors and the reproducibility fixture (not the fuzz cases)
+        python tools/gen_golden.py 'fuzz_*' 'wide_*'    every fuzz case;  wide_07: that one
 """
 import copy
 import json
@@ -28,6 +34,11 @@ import refload  # noqa: E402
 env_mod, mg, rparser, rmap, td, const = refload.load()
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(REPO, "tests", "golden")
+FUZZ_OUT = os.path.join(OUT, "fuzz")
+for _p in (REPO, os.path.join(REPO, "tests")):
+    if _p not in sys.path:
+        sys.path.append(_p)
+import fuzz_configs  # noqa: E402  (tests/fuzz_configs.py)
 TESTDATA = "/root/reference/tests/test_data"
 ROUTES = sorted({f.split()[1] for t in td.TRAFFIC_LANES.values() for c in t for s in c for f in s
                  if f.startswith("car_lane") and f.split()[1] != "all"})
@@ -94,6 +105,28 @@ CONFIGS = {
 }
 
 
+# ---- the fuzz distributions of tests/fuzz_configs.py ------------------------------------------------
+# wide_kwargs(k) for these k: chosen so that the recorded data meets the conditions that
+# tests/test_oracle_fuzz.py asserts of the set (every case ends an episode; maps of more than 64
+# tiles, strips, random start and goal, windows of 1, 6 and 7, dense traffic, braking, every obstacle
+# type, a cost) and that every step-kernel instance gets several configurations.  0..40 but for 4, 8,
+# 10 and 37 (the reference takes more than 5 s for each: large maps with large windows); 43 and 50 for
+# the map-queue kernels on maps of up to 64 tiles, 76 for a map above 64 tiles with lane channels.  No
+# k was left out because the reference raised.
+WIDE_KS = [k for k in range(41) if k not in (4, 8, 10, 37)] + [43, 50, 76]
+FUZZ_STEPS = 25
+
+
+def _fuzz_cases():
+    """name: (kwargs, map_path, n_envs, steps, action_mode); by k, so that a case does not depend on
+    which others are in the table: 4, 4, 3, 3 envs and uniform, cautious actions in turn"""
+    draws = [(f"fuzz_{k:02d}", k, fuzz_configs.random_kwargs(k)) for k in range(40)]
+    draws += [(f"wide_{k:02d}", k, fuzz_configs.wide_kwargs(k)) for k in WIDE_KS]
+    return {name: (kw, None, 4 if k % 4 < 2 else 3, FUZZ_STEPS, "uniform" if k % 2 == 0 else "cautious")
+            for name, k, kw in draws}
+
+
+FUZZ_CASES = _fuzz_cases()
 
 
 # ---- cases with their own traffic rules ------------------------------------------------------------
@@ -249,6 +282,8 @@ def run(name, write=True, seeds=None):
         if seeds:  # (a seed search, write=False)
             seed_base, act_seed = seeds
         rules = RULE_SETS[rule_set]
+    elif name in FUZZ_CASES:
+        kwargs, map_file, N, T, mode = FUZZ_CASES[name]
     else:
         kwargs, map_file, N, T, mode = CONFIGS[name]
     map_path = os.path.join(TESTDATA, map_file) if map_file else None
@@ -266,7 +301,14 @@ def run(name, write=True, seeds=None):
     rule_names = [r.name for r in envs[0].rule_engine.rules]
     first = [e.reset(seed=seed_base + i)[0] for i, e in enumerate(envs)]
     keys = list(first[0]["map"].keys())
-    W = np.asarray(first[0]["map"][keys[0]]).shape[0]
+    # The reference adds the generic features by iterating over a set of their names, so their order
+    # changes with the interpreter's string hashing: record them in the order of the feature list
+    # instead (a regenerated fixture is then the same file; the tests map keys to channels by name).
+    feats = list(envs[0].features_to_include_in_observation)
+    lights = [f"traffic_light_{c}" for c in ("green", "yellow", "red")] if "traffic_light" in feats else []
+    generic = [k for k in keys if k in feats and k not in ["walls", "goals", "traffic"] + lights]
+    keys = [k for k in keys if k not in generic] + sorted(generic, key=feats.index)
+    W =np.asarray(first[0]["map"][keys[0]]).shape[0]
     C = len(keys)
     init_obs = np.stack([obs_stack(o, keys) for o in first])
     init_pos = np.array([o["position"] for o in first], np.int32)
@@ -323,7 +365,7 @@ def run(name, write=True, seeds=None):
     if not write:
         return trig
     np.savez_compressed(
-        os.path.join(OUT, f"traj_{name}.npz"),
+        os.path.join(FUZZ_OUT if name in FUZZ_CASES else OUT, f"traj_{name}.npz"),
         meta=np.frombuffer(json.dumps(meta).encode(), np.uint8), actions=acts,
         init_obs=init_obs, init_pos=init_pos, init_nsd=init_nsd,
         init_cars_dig=np.array([digest(c) for c in init_cars], np.uint32),
@@ -400,8 +442,15 @@ def rng_vectors():
 
 
 if __name__ == "__main__":
-    os.makedirs(OUT, exist_ok=True)
-    names = sys.argv[1:] or list(CONFIGS) + list(RULE_CASES)
+    os.makedirs(FUZZ_OUT, exist_ok=True)
+    every = list(CONFIGS) + list(RULE_CASES) + list(FUZZ_CASES)
+    names = []
+    for a in sys.argv[1:]:  # a name, or a prefix with a trailing *
+        hit = [n for n in every if n.startswith(a[:-1])] if a.endswith("*") else [a]
+        if not hit or hit[0] not in every:
+            sys.exit(f"no case {a!r}")
+        names += hit
+    names = names or list(CONFIGS) + list(RULE_CASES)
     if not sys.argv[1:]:
         rng_vectors()
         reproducibility_fixture()
