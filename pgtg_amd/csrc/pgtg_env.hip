@@ -6448,8 +6448,29 @@ int pgtg_gae(pgtg_handle* h, const PgtgGae* a) {
 // The MlpPolicy forward pass (pgtg_policy.h): the handle gives the device, the stream and the error string
 int pgtg_policy_chunk(void) { return kPolChunk; }
 
+// The public structs of twelve pointers (PgtgPolicyWeights, PgtgPpoGrads, PgtgPpoConstGrads) share their
+// field names with the kernels' PolicyTensors: all twelve set, and the copy of one into another
+static const auto all12 = [](const auto& s) {
+  return s.w1p && s.b1p && s.w2p && s.b2p && s.wa && s.ba && s.w1v && s.b1v && s.w2v && s.b2v && s.wv && s.bv;
+};
+static const auto put12 = [](auto& d, const auto& s) {
+  d.w1p = s.w1p, d.b1p = s.b1p, d.w2p = s.w2p, d.b2p = s.b2p, d.wa = s.wa, d.ba = s.ba;
+  d.w1v = s.w1v, d.b1v = s.b1v, d.w2v = s.w2v, d.b2v = s.b2v, d.wv = s.wv, d.bv = s.bv;
+};
+
+// The two refusals every entry point of the policy and of PPO shares, under the entry point's name `fn`
+static bool obs_dim_ok(uint64_t obs_dim) { return obs_dim >= 1 && obs_dim <= kPolMaxObsDim; }
+static int check_obs_dim(pgtg_handle* h, const char* fn, uint64_t obs_dim) {
+  if (obs_dim_ok(obs_dim)) return PGTG_OK;
+  return fail(h, PGTG_E_INVALID, std::string(fn) + ": obs_dim outside [1, PGTG_POLICY_MAX_OBS_DIM]");
+}
+static int check_packed(pgtg_handle* h, const char* fn, const void* packed) {
+  if (!((uintptr_t)packed & 15u)) return PGTG_OK;
+  return fail(h, PGTG_E_INVALID, std::string(fn) + ": packed must be 16-byte aligned");
+}
+
 int pgtg_policy_packed_bytes(uint64_t obs_dim, uint64_t* bytes) {
-  if (!bytes || obs_dim == 0 || obs_dim > kPolMaxObsDim) return PGTG_E_INVALID;
+  if (!bytes || !obs_dim_ok(obs_dim)) return PGTG_E_INVALID;
   *bytes = policy_layout(obs_dim).total * sizeof(float);
   return PGTG_OK;
 }
@@ -6457,14 +6478,13 @@ int pgtg_policy_packed_bytes(uint64_t obs_dim, uint64_t* bytes) {
 int pgtg_policy_pack(pgtg_handle* h, const PgtgPolicyWeights* raw, void* packed) {
   if (!h) return PGTG_E_INVALID;
   if (!raw || !packed) return fail(h, PGTG_E_INVALID, "pgtg_policy_pack: no weights or no packed buffer");
-  if (raw->obs_dim == 0 || raw->obs_dim > kPolMaxObsDim)
-    return fail(h, PGTG_E_INVALID, "pgtg_policy_pack: obs_dim outside [1, PGTG_POLICY_MAX_OBS_DIM]");
-  if (!raw->w1p || !raw->b1p || !raw->w2p || !raw->b2p || !raw->wa || !raw->ba || !raw->w1v || !raw->b1v ||
-      !raw->w2v || !raw->b2v || !raw->wv || !raw->bv)
-    return fail(h, PGTG_E_INVALID, "pgtg_policy_pack: all twelve weight pointers are required");
-  if ((uintptr_t)packed & 15u) return fail(h, PGTG_E_INVALID, "pgtg_policy_pack: packed must be 16-byte aligned");
-  PolicyPackArgs p = {raw->w1p, raw->b1p, raw->w2p, raw->b2p, raw->wa, raw->ba, raw->w1v, raw->b1v,
-                      raw->w2v, raw->b2v, raw->wv,  raw->bv,  (float*)packed, raw->obs_dim};
+  if (int e = check_obs_dim(h, "pgtg_policy_pack", raw->obs_dim)) return e;
+  if (!all12(*raw)) return fail(h, PGTG_E_INVALID, "pgtg_policy_pack: all twelve weight pointers are required");
+  if (int e = check_packed(h, "pgtg_policy_pack", packed)) return e;
+  PolicyPackArgs p;
+  put12(p.src, *raw);
+  p.out = (float*)packed;
+  p.obs_dim = raw->obs_dim;
   const uint64_t total = policy_layout(raw->obs_dim).total;
   const uint64_t grid = std::min<uint64_t>((total + 255) / 256, 4096);
   HIPCHK(h, hipSetDevice(h->device));
@@ -6480,7 +6500,7 @@ int pgtg_policy(pgtg_handle* h, const PgtgPolicy* a) {
   if (a->obs_dim > kPolMaxObsDim)
     return fail(h, PGTG_E_INVALID, "pgtg_policy: obs_dim beyond PGTG_POLICY_MAX_OBS_DIM, the largest the pack supports");
   if (!a->obs || !a->packed) return fail(h, PGTG_E_INVALID, "pgtg_policy: obs and packed are required");
-  if ((uintptr_t)a->packed & 15u) return fail(h, PGTG_E_INVALID, "pgtg_policy: packed must be 16-byte aligned");
+  if (int e = check_packed(h, "pgtg_policy", a->packed)) return e;
   if (a->mode != PGTG_POLICY_SAMPLE && a->mode != PGTG_POLICY_ARGMAX && a->mode != PGTG_POLICY_VALUE_ONLY)
     return fail(h, PGTG_E_INVALID, "pgtg_policy: mode 0 sample, 1 argmax, 2 value only");
   if (a->mode == PGTG_POLICY_VALUE_ONLY && !a->values)
@@ -6514,7 +6534,7 @@ int pgtg_policy(pgtg_handle* h, const PgtgPolicy* a) {
 // One PPO minibatch gradient (pgtg_ppo.h): the handle gives the device, the stream, the error string and
 // the error bytes that count the skipped samples
 int pgtg_ppo_workspace_bytes(uint64_t obs_dim, uint64_t batch, uint64_t* bytes) {
-  if (!bytes || obs_dim == 0 || obs_dim > kPolMaxObsDim) return PGTG_E_INVALID;
+  if (!bytes || !obs_dim_ok(obs_dim)) return PGTG_E_INVALID;
   if (batch > (UINT64_MAX >> 12) / obs_dim) return PGTG_E_INVALID;  // (segments <= blocks: total < 2^11 batch obs_dim floats)
   *bytes = batch ? ppo_plan(batch, obs_dim).total * sizeof(float) : 0;
   return PGTG_OK;
@@ -6523,16 +6543,13 @@ int pgtg_ppo_workspace_bytes(uint64_t obs_dim, uint64_t batch, uint64_t* bytes) 
 int pgtg_ppo_grad(pgtg_handle* h, const PgtgPpoGrad* a) {
   if (!h) return PGTG_E_INVALID;
   if (!a) return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: no arguments");
-  if (a->obs_dim == 0 || a->obs_dim > kPolMaxObsDim)
-    return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: obs_dim outside [1, PGTG_POLICY_MAX_OBS_DIM]");
+  if (int e = check_obs_dim(h, "pgtg_ppo_grad", a->obs_dim)) return e;
   if (a->steps == 0 || a->n == 0) return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: steps and n must be at least 1");
-  const PgtgPpoGrads& g = a->grads;
   if (!a->obs || !a->indices || !a->actions || !a->log_probs || !a->advantages || !a->returns || !a->packed ||
       !a->workspace || !a->stats)
     return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: obs, indices, the rollout arrays, packed, workspace and stats are required");
-  if (!g.w1p || !g.b1p || !g.w2p || !g.b2p || !g.wa || !g.ba || !g.w1v || !g.b1v || !g.w2v || !g.b2v || !g.wv || !g.bv)
-    return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: all twelve gradient pointers are required");
-  if ((uintptr_t)a->packed & 15u) return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: packed must be 16-byte aligned");
+  if (!all12(a->grads)) return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: all twelve gradient pointers are required");
+  if (int e = check_packed(h, "pgtg_ppo_grad", a->packed)) return e;
   if ((uintptr_t)a->workspace & 15u) return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: workspace must be 16-byte aligned");
   if (a->n > (UINT64_MAX >> 1) / a->obs_dim || a->steps > (UINT64_MAX >> 1) / a->n)
     return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: n * obs_dim or steps * n overflows");
@@ -6570,7 +6587,7 @@ int pgtg_ppo_grad(pgtg_handle* h, const PgtgPpoGrad* a) {
   p.ws = (float*)a->workspace;
   p.err = h->S.err;
   p.err_n = h->S.err ? h->n : 0;
-  p.g = a->grads;
+  put12(p.g, a->grads);
   p.stats = a->stats;
   HIPCHK(h, hipSetDevice(h->device));
   hipLaunchKernelGGL(k_ppo_loss, dim3((unsigned)pl.blocks), dim3(kPpoThreads), 0, h->stream, p);
@@ -6583,7 +6600,7 @@ int pgtg_ppo_grad(pgtg_handle* h, const PgtgPpoGrad* a) {
 // The optimiser step of a PPO minibatch and the advantage statistics (pgtg_ppo_step.h): the handle gives the
 // device, the stream and the error string
 int pgtg_ppo_step_workspace_bytes(uint64_t obs_dim, uint64_t* bytes) {
-  if (!bytes || obs_dim == 0 || obs_dim > kPolMaxObsDim) return PGTG_E_INVALID;
+  if (!bytes || !obs_dim_ok(obs_dim)) return PGTG_E_INVALID;
   *bytes = (step_blocks(obs_dim) * sizeof(double) + 15) & ~(uint64_t)15;
   return PGTG_OK;
 }
@@ -6604,15 +6621,11 @@ static double widen_decimal(float x) {
 int pgtg_ppo_step(pgtg_handle* h, const PgtgPpoStep* a) {
   if (!h) return PGTG_E_INVALID;
   if (!a) return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: no arguments");
-  if (a->obs_dim == 0 || a->obs_dim > kPolMaxObsDim)
-    return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: obs_dim outside [1, PGTG_POLICY_MAX_OBS_DIM]");
-  auto all12 = [](const auto& s) {
-    return s.w1p && s.b1p && s.w2p && s.b2p && s.wa && s.ba && s.w1v && s.b1v && s.w2v && s.b2v && s.wv && s.bv;
-  };
+  if (int e = check_obs_dim(h, "pgtg_ppo_step", a->obs_dim)) return e;
   if (!all12(a->params) || !all12(a->grads) || !all12(a->exp_avg) || !all12(a->exp_avg_sq))
     return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: all twelve pointers of params, grads, exp_avg and exp_avg_sq are required");
   if (!a->packed || !a->workspace) return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: packed and workspace are required");
-  if ((uintptr_t)a->packed & 15u) return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: packed must be 16-byte aligned");
+  if (int e = check_packed(h, "pgtg_ppo_step", a->packed)) return e;
   if ((uintptr_t)a->workspace & 7u) return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: workspace must be 8-byte aligned");
   if (a->step == 0) return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: step counts from 1");
   if (!std::isfinite(a->lr) || !std::isfinite(a->eps) || !std::isfinite(a->beta1) || !std::isfinite(a->beta2))
@@ -6622,14 +6635,10 @@ int pgtg_ppo_step(pgtg_handle* h, const PgtgPpoStep* a) {
   if (!(a->max_grad_norm > 0.f))
     return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: max_grad_norm must be above 0 (+inf: no clip)");
   PpoStepArgs p;
-  auto put = [](auto& d, const auto& s) {
-    d.w1p = s.w1p, d.b1p = s.b1p, d.w2p = s.w2p, d.b2p = s.b2p, d.wa = s.wa, d.ba = s.ba;
-    d.w1v = s.w1v, d.b1v = s.b1v, d.w2v = s.w2v, d.b2v = s.b2v, d.wv = s.wv, d.bv = s.bv;
-  };
-  put(p.p, a->params);
-  put(p.g, a->grads);
-  put(p.m, a->exp_avg);
-  put(p.v, a->exp_avg_sq);
+  put12(p.p, a->params);
+  put12(p.g, a->grads);
+  put12(p.m, a->exp_avg);
+  put12(p.v, a->exp_avg_sq);
   p.packed = (float*)a->packed;
   p.ws = (double*)a->workspace;
   p.grad_norm = a->grad_norm;

@@ -1,10 +1,10 @@
 // pgtg_ppo.h -- one PPO minibatch of SB3's PPO.train (defaults, clip_range_vf = None) over a finished
 // rollout's int8 rows: the loss, its six statistics and the gradient with respect to the twelve MlpPolicy
 // tensors (include/pgtg.h pgtg_ppo_grad).  Three kernels and no floating-point atomic:
-//   k_ppo_loss    64 samples per workgroup: gathers their rows, runs k_policy's forward (the same tiling and
-//                 the same order of operations, restated here so that k_policy's own code does not move), the
-//                 heads, the loss terms and the backward pass down to dZ1 [64][128]; writes dZ1 and the
-//                 workgroup's partial sums of every gradient but W1's to its own workspace slot
+//   k_ppo_loss    64 samples per workgroup: gathers their rows, runs k_policy's forward and heads (the functions
+//                 of pgtg_policy.h themselves: the log-probs a rollout stored are the ones recomputed here), the
+//                 loss terms and the backward pass down to dZ1 [64][128]; writes dZ1 and the workgroup's partial
+//                 sums of every gradient but W1's to its own workspace slot
 //   k_ppo_dw1     dW1 [128][D] = dZ1^T X on v_mfma_f32_16x16x4_f32: a workgroup owns 128 observation columns
 //                 and one segment of the batch, gathers the int8 rows again and converts them in registers
 //   k_ppo_reduce  sums the slots and the segments in a fixed order into the twelve tensors and the statistics
@@ -62,19 +62,17 @@ struct PpoArgs {
   float* ws;
   uint8_t* err;      // the handle's per-env error bytes, err_n of them
   uint64_t err_n;
-  PgtgPpoGrads g;
+  PolicyTensors<float> g;
   float* stats;
 };
 
-// The four bytes k .. k + 3 (k < D) of the row at byte address `row`, bytes at k >= D zero, assembled from
-// the two aligned dwords around them; no byte outside [lo, hi) is touched.
-__device__ __forceinline__ uint32_t ppo_row_dword(uintptr_t row, uint64_t k, uint64_t D, uintptr_t lo, uintptr_t hi) {
-  const uintptr_t p = row + k, al = p & ~(uintptr_t)3;
-  const uint32_t sh = (uint32_t)(p & 3) * 8;
-  uint32_t v = policy_load_dword(al, lo, hi);
-  if (sh) v = (v >> sh) | (policy_load_dword(al + 4, lo, hi) << (32 - sh));
-  if (k + 4 > D) v &= 0xffffffffu >> (8 * (uint32_t)(k + 4 - D));
-  return v;
+// Sample idx of a rollout of T steps of N envs (SB3's flat order, env-major): its env and its step; false for
+// an index outside [0, T N), which no kernel dereferences.
+__device__ __forceinline__ bool ppo_sample(int64_t idx, uint64_t T, uint64_t N, uint64_t* env, uint64_t* step) {
+  if (idx < 0 || (uint64_t)idx >= T * N) return false;
+  *env = (uint64_t)idx / T;
+  *step = (uint64_t)idx % T;
+  return true;
 }
 
 // sum of n floats p[0], p[stride], ...: kPpoSets accumulators take them round robin, added (0 + 1) + (2 + 3)
@@ -99,7 +97,7 @@ __device__ __forceinline__ float ppo_sum_rows(F f) {
 }
 
 __global__ void __launch_bounds__(kPpoThreads) k_ppo_loss(PpoArgs a) {
-  // h1 [64][kPolHPitch], then h2 the same with the staged observation bytes over it, as in k_policy
+  // h1 [64][kPolHPitch], then h2 the same, as in k_policy
   __shared__ __attribute__((aligned(16))) float lds[2 * kPpoRows * kPolHPitch];
   __shared__ float sdl[kPpoRows * 12];  // per sample: dloss/dlogit [9], dloss/dvalue at [9]
   __shared__ float sst[kPpoRows * 8];   // per sample: the five statistics' terms
@@ -108,18 +106,13 @@ __global__ void __launch_bounds__(kPpoThreads) k_ppo_loss(PpoArgs a) {
   __shared__ uint64_t soff[kPpoRows];   // t * N + e
   float* h1 = lds;
   float* h2 = lds + kPpoRows * kPolHPitch;
-  uint8_t* xs = (uint8_t*)h2;
   static_assert(kPpoRows == kPolRows && kPpoThreads == kPolThreads, "k_policy's tiling");
-  static_assert(kPolChunk == 256, "the stage takes dword idx & 63 of row idx >> 6");
-  static_assert(kPolRows * kPolXPitch <= kPolRows * kPolHPitch * 4, "the staged rows fit under h2");
 
-  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const uint32_t n16 = lane & 15, q = lane >> 4;
+  const uint32_t tid = threadIdx.x, w = tid >> 6;
   const uint64_t D = a.D, B = a.B, blk = blockIdx.x;
   const PolicyLayout L = policy_layout(D);
   const PpoPlan pl = ppo_plan(B, D);
   const float* P = a.packed;
-  const uint32_t cb = 32 * w;
   const uintptr_t lo = (uintptr_t)a.obs, hi = lo + (a.T - 1) * a.pitch + a.N * D;
   float* slot = a.ws + pl.part_a + blk * kPpoSlot;
 
@@ -127,9 +120,8 @@ __global__ void __launch_bounds__(kPpoThreads) k_ppo_loss(PpoArgs a) {
     const uint64_t s = blk * kPpoRows + tid;
     uint64_t rp = 0, so = 0;
     if (s < B) {
-      const int64_t idx = a.indices[s];
-      if (idx >= 0 && (uint64_t)idx < a.T * a.N) {
-        const uint64_t e = (uint64_t)idx / a.T, t = (uint64_t)idx % a.T;
+      uint64_t e, t;
+      if (ppo_sample(a.indices[s], a.T, a.N, &e, &t)) {
         so = t * a.N + e;
         if (a.actions[so] < kPolAct) rp = lo + t * a.pitch + e * D;
       }
@@ -140,123 +132,14 @@ __global__ void __launch_bounds__(kPpoThreads) k_ppo_loss(PpoArgs a) {
   }
   __syncthreads();
 
-  // ---- layer 1: k_policy's, over gathered rows ----------------------------------------------------
-  pol_f32x4 acc[kPolSets][4][2];
-#pragma unroll
-  for (int s = 0; s < kPolSets; s++)
-#pragma unroll
-    for (int m = 0; m < 4; m++)
-#pragma unroll
-      for (int j = 0; j < 2; j++) acc[s][m][j] = pol_f32x4{0.f, 0.f, 0.f, 0.f};
-  const uint64_t chunks = (D + kPolChunk - 1) / kPolChunk;
-  for (uint64_t ch = 0; ch < chunks; ch++) {
-    const uint64_t k0 = ch * kPolChunk;
-    if (ch) __syncthreads();
-#pragma unroll 4
-    for (int it = 0; it < kPpoRows * (kPolChunk / 4) / kPpoThreads; it++) {
-      const uint32_t idx = it * kPpoThreads + tid, r = idx >> 6, dw = idx & 63;
-      const uint64_t k = k0 + 4 * dw, rp = rowp[r];
-      uint32_t v = 0;
-      if (rp && k < D) v = ppo_row_dword((uintptr_t)rp, k, D, lo, hi);
-      *(uint32_t*)(xs + r * kPolXPitch + 4 * dw) = v;
-    }
-    __syncthreads();
-    const uint64_t g0 = k0 / 16;
-    const uint64_t gn = L.groups - g0 < (uint64_t)(kPolChunk / 16) ? L.groups - g0 : (uint64_t)(kPolChunk / 16);
-    for (uint64_t gb = 0; gb < gn; gb += kPolSets) {
-#pragma unroll
-      for (int s = 0; s < kPolSets; s++) {
-        const uint64_t gl = gb + s;
-        if (gl < gn) {
-          const float* wg = P + L.w1 + ((g0 + gl) * 128 + cb + n16) * 16 + 4 * q;
-          pol_f32x4 b[2];
-#pragma unroll
-          for (int j = 0; j < 2; j++) b[j] = *(const pol_f32x4*)(wg + j * 256);
-          uint32_t xa[4];
-#pragma unroll
-          for (int m = 0; m < 4; m++) xa[m] = *(const uint32_t*)(xs + (16 * m + n16) * kPolXPitch + 16 * gl + 4 * q);
-#pragma unroll
-          for (int st = 0; st < 4; st++)
-#pragma unroll
-            for (int m = 0; m < 4; m++) {
-              const float x = (float)(int)(int8_t)(xa[m] >> (8 * st));
-#pragma unroll
-              for (int j = 0; j < 2; j++)
-                acc[s][m][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(x, b[j][st], acc[s][m][j], 0, 0, 0);
-            }
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 2; j++) {
-    const uint32_t c = cb + 16 * j + n16;
-    const float bias = P[L.b1 + c];
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-      const pol_f32x4 t = (acc[0][m][j] + acc[1][m][j]) + (acc[2][m][j] + acc[3][m][j]);
-#pragma unroll
-      for (int i = 0; i < 4; i++) h1[(16 * m + 4 * q + i) * kPolHPitch + c] = tanhf(t[i] + bias);
-    }
-  }
-  __syncthreads();
+  // ---- the forward pass (pgtg_policy.h), over the gathered rows ------------------------------------------
+  policy_hidden<2>(P, L, D, lo, hi, 32 * w, h1, h2, [&](uint32_t r, uintptr_t* p) { return (*p = rowp[r]) != 0; });
 
-  // ---- layer 2: k_policy's ------------------------------------------------------------------------
-  {
-    const uint32_t tower = cb >> 6, c2 = cb & 63;
-    pol_f32x4 a2[4][2];
-#pragma unroll
-    for (int m = 0; m < 4; m++)
-#pragma unroll
-      for (int j = 0; j < 2; j++) a2[m][j] = pol_f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-      const float* wg = P + L.w2 + (((uint64_t)tower * 4 + g) * 64 + c2 + n16) * 16 + 4 * q;
-      pol_f32x4 b[2], x[4];
-#pragma unroll
-      for (int j = 0; j < 2; j++) b[j] = *(const pol_f32x4*)(wg + j * 256);
-#pragma unroll
-      for (int m = 0; m < 4; m++) x[m] = *(const pol_f32x4*)(h1 + (16 * m + n16) * kPolHPitch + 64 * tower + 16 * g + 4 * q);
-#pragma unroll
-      for (int st = 0; st < 4; st++)
-#pragma unroll
-        for (int m = 0; m < 4; m++)
-#pragma unroll
-          for (int j = 0; j < 2; j++)
-            a2[m][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[m][st], b[j][st], a2[m][j], 0, 0, 0);
-    }
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-      const uint32_t c = cb + 16 * j + n16;
-      const float bias = P[L.b2 + c];
-#pragma unroll
-      for (int m = 0; m < 4; m++)
-#pragma unroll
-        for (int i = 0; i < 4; i++) h2[(16 * m + 4 * q + i) * kPolHPitch + c] = tanhf(a2[m][j][i] + bias);
-    }
-  }
-  __syncthreads();
-
-  // ---- heads (k_policy's: four lanes per sample), the loss terms and their derivatives ----------------
+  // ---- the heads, the loss terms and their derivatives -------------------------------------------------
   {
     const uint32_t r = tid >> 2, part = tid & 3;
-    const float* hp = h2 + r * kPolHPitch + 16 * part;
-    float val = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; k++) val += P[L.wv + 16 * part + k] * hp[64 + k];
-    val += __shfl_xor(val, 1);
-    val += __shfl_xor(val, 2);
-    val += P[L.bv];
-    float lg[kPolAct];
-#pragma unroll
-    for (int c = 0; c < kPolAct; c++) {
-      float s = 0.f;
-#pragma unroll
-      for (int k = 0; k < 16; k++) s += P[L.wa + c * 64 + 16 * part + k] * hp[k];
-      s += __shfl_xor(s, 1);
-      s += __shfl_xor(s, 2);
-      lg[c] = s + P[L.ba + c];
-    }
+    float val, lg[kPolAct];
+    policy_heads<false>(P, L, h2, r, part, &val, lg);
     if (part == 0) {
       float dl[kPolAct + 1], st[kPpoStats];
 #pragma unroll
@@ -267,16 +150,8 @@ __global__ void __launch_bounds__(kPpoThreads) k_ppo_loss(PpoArgs a) {
         const uint64_t so = soff[r];
         const int act = a.actions[so];
         const float inv_b = 1.f / (float)B;
-        float mx = lg[0];
-#pragma unroll
-        for (int c = 1; c < kPolAct; c++)
-          if (lg[c] > mx) mx = lg[c];
-        float ex[kPolAct], sum = 0.f;
-#pragma unroll
-        for (int c = 0; c < kPolAct; c++) {
-          ex[c] = expf(lg[c] - mx);
-          sum += ex[c];
-        }
+        float mx, ex[kPolAct], sum;
+        policy_softmax(lg, &mx, ex, &sum);
         const float lse = mx + logf(sum);
         float la = lg[0];
 #pragma unroll
@@ -433,10 +308,8 @@ __global__ void __launch_bounds__(kPpoThreads) k_ppo_dw1(PpoArgs a) {
     if (tid < kPpoRows) {
       const uint64_t s = blk * kPpoRows + tid;
       uint64_t rp = 0;
-      if (s < B) {
-        const int64_t idx = a.indices[s];
-        if (idx >= 0 && (uint64_t)idx < a.T * a.N) rp = lo + ((uint64_t)idx % a.T) * a.pitch + ((uint64_t)idx / a.T) * D;
-      }
+      uint64_t e, t;
+      if (s < B && ppo_sample(a.indices[s], a.T, a.N, &e, &t)) rp = lo + t * a.pitch + e * D;
       rowp[tid] = rp;
     }
     const float* src = a.ws + pl.dz1 + blk * kPpoRows * 128;
@@ -451,7 +324,7 @@ __global__ void __launch_bounds__(kPpoThreads) k_ppo_dw1(PpoArgs a) {
       const uint32_t i = it * kPpoThreads + tid, r = i >> 5, dw = i & 31;
       const uint64_t k = k0 + 4 * dw, rp = rowp[r];
       uint32_t v = 0;
-      if (rp && k < D) v = ppo_row_dword((uintptr_t)rp, k, D, lo, hi);
+      if (rp && k < D) v = policy_row_dword((uintptr_t)rp, k, D, lo, hi);
       *(uint32_t*)(xs + r * kPpoXPitch + 4 * dw) = v;
     }
     __syncthreads();

@@ -6,7 +6,7 @@
 // a few adds per thread and a tree: the results are the float32 roundings of sums that carry no error of
 // their own, which is what lets them stand within torch's float32 error of the float64 truth).
 //   k_ppo_gnorm      per-workgroup partial sums of g^2 over the twelve gradient tensors, to the workspace
-//   k_ppo_adam       one thread per word of the packed buffer (k_policy_pack's index walk): every workgroup
+//   k_ppo_adam       one thread per word of the packed buffer (policy_packed_word, as k_policy_pack): every workgroup
 //                    adds the partials in the same order, then clip, Adam and the packed word
 //   k_ppo_adv_stats  one workgroup: the gathered advantages' mean, then their squared deviations
 // Included by pgtg_env.hip (device code only) after pgtg_ppo.h.
@@ -33,16 +33,9 @@ __host__ __device__ inline uint64_t step_blocks(uint64_t D) {
   return b < (uint64_t)kStepMaxBlocks ? b : (uint64_t)kStepMaxBlocks;
 }
 
-struct StepTensors {
-  float *w1p, *b1p, *w2p, *b2p, *wa, *ba, *w1v, *b1v, *w2v, *b2v, *wv, *bv;
-};
-struct StepConstTensors {
-  const float *w1p, *b1p, *w2p, *b2p, *wa, *ba, *w1v, *b1v, *w2v, *b2v, *wv, *bv;
-};
-
 struct PpoStepArgs {
-  StepTensors p, m, v;
-  StepConstTensors g;
+  PolicyTensors<float> p, m, v;
+  PolicyTensors<const float> g;
   float* packed;
   double* ws;  // step_blocks(D) partial sums
   float* grad_norm;
@@ -52,69 +45,21 @@ struct PpoStepArgs {
   float max_norm;
 };
 
-enum { ST_W1P, ST_B1P, ST_W2P, ST_B2P, ST_WA, ST_BA, ST_W1V, ST_B1V, ST_W2V, ST_B2V, ST_WV, ST_BV };
-
-template <typename T>
-__device__ __forceinline__ auto step_tensor(const T& s, int t) -> decltype(s.w1p) {
-  switch (t) {
-    case ST_W1P: return s.w1p;
-    case ST_B1P: return s.b1p;
-    case ST_W2P: return s.w2p;
-    case ST_B2P: return s.b2p;
-    case ST_WA: return s.wa;
-    case ST_BA: return s.ba;
-    case ST_W1V: return s.w1v;
-    case ST_B1V: return s.b1v;
-    case ST_W2V: return s.w2v;
-    case ST_B2V: return s.b2v;
-    case ST_WV: return s.wv;
-    default: return s.bv;
-  }
-}
-
 // element i of the twelve tensors end to end (step_params' order): its tensor and its offset there
 __device__ __forceinline__ int step_linear(uint64_t i, uint64_t D, uint64_t* off) {
-  if (i < 64 * D) return *off = i, ST_W1P;
-  if (i < 128 * D) return *off = i - 64 * D, ST_W1V;
+  if (i < 64 * D) return *off = i, PT_W1P;
+  if (i < 128 * D) return *off = i - 64 * D, PT_W1V;
   uint64_t j = i - 128 * D;
-  if (j < 64) return *off = j, ST_B1P;
-  if ((j -= 64) < 64) return *off = j, ST_B1V;
-  if ((j -= 64) < 4096) return *off = j, ST_W2P;
-  if ((j -= 4096) < 4096) return *off = j, ST_W2V;
-  if ((j -= 4096) < 64) return *off = j, ST_B2P;
-  if ((j -= 64) < 64) return *off = j, ST_B2V;
-  if ((j -= 64) < (uint64_t)(kPolAct * kPolHid)) return *off = j, ST_WA;
-  if ((j -= kPolAct * kPolHid) < (uint64_t)kPolAct) return *off = j, ST_BA;
-  if ((j -= kPolAct) < (uint64_t)kPolHid) return *off = j, ST_WV;
-  return *off = 0, ST_BV;
-}
-
-// word i of the packed buffer (policy_layout; the walk of k_policy_pack): its tensor and its offset there,
-// -1 for a padding word (k >= D of the last W1 group, the pads after ba and bv)
-__device__ __forceinline__ int step_packed(uint64_t i, const PolicyLayout& L, uint64_t D, uint64_t* off) {
-  if (i < L.b1) {
-    const uint64_t g = i / 2048, c = (i / 16) % 128, k = g * 16 + (i % 16);
-    if (k >= D) return -1;
-    return c < 64 ? (*off = c * D + k, ST_W1P) : (*off = (c - 64) * D + k, ST_W1V);
-  }
-  if (i < L.w2) {
-    const uint64_t c = i - L.b1;
-    return c < 64 ? (*off = c, ST_B1P) : (*off = c - 64, ST_B1V);
-  }
-  if (i < L.b2) {
-    const uint64_t j = i - L.w2, t = j / 4096, g = (j / 1024) % 4, c = (j / 16) % 64, k = g * 16 + (j % 16);
-    *off = c * 64 + k;
-    return t ? ST_W2V : ST_W2P;
-  }
-  if (i < L.wa) {
-    const uint64_t c = i - L.b2;
-    return c < 64 ? (*off = c, ST_B2P) : (*off = c - 64, ST_B2V);
-  }
-  if (i < L.ba) return *off = i - L.wa, ST_WA;
-  if (i < L.wv) return i - L.ba < (uint64_t)kPolAct ? (*off = i - L.ba, ST_BA) : -1;
-  if (i < L.bv) return *off = i - L.wv, ST_WV;
-  if (i == L.bv) return *off = 0, ST_BV;
-  return -1;
+  if (j < 64) return *off = j, PT_B1P;
+  if ((j -= 64) < 64) return *off = j, PT_B1V;
+  if ((j -= 64) < 4096) return *off = j, PT_W2P;
+  if ((j -= 4096) < 4096) return *off = j, PT_W2V;
+  if ((j -= 4096) < 64) return *off = j, PT_B2P;
+  if ((j -= 64) < 64) return *off = j, PT_B2V;
+  if ((j -= 64) < (uint64_t)(kPolAct * kPolHid)) return *off = j, PT_WA;
+  if ((j -= kPolAct * kPolHid) < (uint64_t)kPolAct) return *off = j, PT_BA;
+  if ((j -= kPolAct) < (uint64_t)kPolHid) return *off = j, PT_WV;
+  return *off = 0, PT_BV;
 }
 
 // the sum of red[0 .. n) (n a power of two, one value per thread) as a halving tree; every thread returns it
@@ -141,7 +86,7 @@ __global__ void __launch_bounds__(kStepThreads) k_ppo_gnorm(PpoStepArgs a) {
       if (i < n) {
         uint64_t off;
         const int t = step_linear(i, D, &off);
-        const double g = step_tensor(a.g, t)[off];
+        const double g = policy_tensor(a.g, t)[off];
         s[j] += g * g;
       }
     }
@@ -162,13 +107,13 @@ __global__ void __launch_bounds__(kStepThreads) k_ppo_adam(PpoStepArgs a) {
   const uint64_t stride = (uint64_t)gridDim.x * kStepThreads;
   for (uint64_t i = (uint64_t)blockIdx.x * kStepThreads + threadIdx.x; i < L.total; i += stride) {
     uint64_t off = 0;
-    const int t = step_packed(i, L, D, &off);
+    const int t = policy_packed_word(i, L, D, &off);
     float w = 0.f;
     if (t >= 0) {
-      float* pp = step_tensor(a.p, t) + off;
-      float* pm = step_tensor(a.m, t) + off;
-      float* pv = step_tensor(a.v, t) + off;
-      const float g = coef * step_tensor(a.g, t)[off];
+      float* pp = policy_tensor(a.p, t) + off;
+      float* pm = policy_tensor(a.m, t) + off;
+      float* pv = policy_tensor(a.v, t) + off;
+      const float g = coef * policy_tensor(a.g, t)[off];
       float m = *pm, v = *pv;
       m = m + a.w1 * (g - m);
       v = a.beta2 * v + (a.w2 * g) * g;
@@ -191,9 +136,8 @@ struct AdvStatsArgs {
 
 // the advantage of batch position s; an index outside the rollout stands as 0
 __device__ __forceinline__ float adv_gather(const AdvStatsArgs& a, uint64_t s) {
-  const int64_t idx = a.indices[s];
-  if (idx < 0 || (uint64_t)idx >= a.T * a.N) return 0.f;
-  return a.adv[((uint64_t)idx % a.T) * a.N + (uint64_t)idx / a.T];
+  uint64_t e, t;
+  return ppo_sample(a.indices[s], a.T, a.N, &e, &t) ? a.adv[t * a.N + e] : 0.f;
 }
 
 __global__ void __launch_bounds__(kAdvThreads) k_ppo_adv_stats(AdvStatsArgs a) {

@@ -165,8 +165,8 @@ def test_repeats_every_sample_once_and_a_permutation(handle):
 
 def test_the_forward_is_k_policys(handle):
     """old_log_probs = k_policy's own for the same weights and actions: approx_kl and the clip fraction are
-    exactly 0.  (The forward is separate code restating k_policy's order of operations; a copy that drifts from
-    k_policy shows here.)"""
+    exactly 0.  (The forward is k_policy's own code, shared through pgtg_policy.h; this pins the log-probs a
+    rollout stores to the ones k_ppo_loss recomputes, through the gather and the whole call.)"""
     D = 1239
     dv = _dev(handle, D)
     c = dv.c
