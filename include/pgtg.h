@@ -20,6 +20,8 @@
  *                        PPO the reference's caller trains                 pgtg/train.py:61-74
  *   pgtg_policy / pgtg_policy_pack <- (new, no reference function) the acting forward pass of the
  *                        MlpPolicy that PPO collects with                  pgtg/train.py:61-74
+ *   pgtg_eval_step / pgtg_eval_summary <- ModularEvaluator.evaluate for the batch, with the per-env
+ *                        episode quotas of SB3's evaluate_policy           pgtg/evaluator.py:284-339
  *   pgtg_flatten      <- (new, test-oriented) the FlattenObservation kernel alone, over the bound outputs
  *   pgtg_snapshot_*   <- copy.deepcopy(env) / env.clone() for single envs of the batch, on the device
  *                        environment.py:1283-1299, pgtg/evaluator.py:98-110
@@ -485,6 +487,56 @@ int pgtg_ppo_step(pgtg_handle* h, const PgtgPpoStep* a);
  * normalise a batch of one), steps or n of 0, steps * n overflowing: PGTG_E_INVALID, nothing is launched. */
 int pgtg_ppo_adv_stats(pgtg_handle* h, const void* advantages, const void* indices, uint64_t batch, uint64_t steps,
                        uint64_t n, float* out);
+/* Policy evaluation with per-env episode quotas (new; ModularEvaluator.evaluate of pgtg/evaluator.py:284-339
+ * for the batch, counted as SB3's evaluate_policy counts a vector env: env e contributes its first
+ * quota_e = (n_episodes + e) / n episodes (integer division; the quotas sum to n_episodes), so short episodes
+ * are not over-represented).  pgtg_eval_step is one launch of k_eval after a tick: per env e, in fp64 without
+ * fused multiply-add,
+ *   if cnt[e] < quota_e:
+ *     ret[e] += r;  disc[e] += r * g[e];  g[e] *= gamma;  len[e] += 1            (r = reward[e])
+ *     if terminated[e] | truncated[e]:
+ *       k = cnt[e];  row k * n + e of the record arrays = {ret, disc, len, r, step, flags};  cnt[e] = k + 1
+ *       ret[e] = disc[e] = 0;  g[e] = 1;  len[e] = 0
+ * and open_rows[b] = the number of envs e in [256 b, 256 b + 256) with cnt[e] < quota_e afterwards (a plain
+ * store per workgroup; no atomics).  An env at its quota is not touched again.  The caller owns every array
+ * and starts an evaluation with ret = disc = 0, g = 1, len = cnt = 0; the record arrays are [Q][n] with
+ * Q = ceil(n_episodes / n), episode slot major, and hold rows k < cnt[e] only.  flags: bit 0 terminated,
+ * bit 1 truncated.  pgtg_eval_summary reduces the recorded episodes (rows k < cnt[e]) into *out_dev in four
+ * launches (k_eval_reduce and k_eval_final, twice: the means first, then the squared deviations about them)
+ * whose partition depends on n alone and whose sums run in a fixed order: the same records give the same bits
+ * on any device.  workspace: pgtg_eval_workspace_bytes(n, n_episodes) bytes, 8-byte aligned, contents
+ * irrelevant.  Both calls are asynchronous on the handle's stream.  A NULL pointer (pgtg_eval_summary does not
+ * read reward, terminated, truncated, ret, disc, g, len or open_rows), n different from the handle's batch
+ * size, n_episodes == 0, gamma outside [0, 1], or step, Q or Q * n beyond INT32_MAX, INT32_MAX and 2^60:
+ * PGTG_E_INVALID with a message, nothing is launched. */
+typedef struct {
+  uint64_t n, n_episodes;          /* N envs (the handle's), episodes wanted over the batch */
+  uint64_t step;                   /* s: the evaluation step this launch records as end_step */
+  double gamma;
+  const double*  reward;           /* [N] the step's outputs (PgtgOutputs.reward, terminated, truncated) */
+  const uint8_t* terminated;
+  const uint8_t* truncated;
+  double* ret; double* disc; double* g;     /* [N] running undiscounted and discounted return, discount */
+  int32_t* len; int32_t* cnt;               /* [N] running length, episodes recorded */
+  double* rec_return; double* rec_discounted; int32_t* rec_length;        /* [Q][N] */
+  double* rec_last_reward; int32_t* rec_end_step; uint8_t* rec_flags;     /* [Q][N] */
+  int32_t* open_rows;              /* [ceil(N / 256)] */
+} PgtgEval;
+/* The recorded episodes.  std: the population standard deviation (numpy's std, ddof 0). */
+typedef struct {
+  uint64_t episodes, open_envs;                          /* open_envs: envs with cnt < quota */
+  uint64_t terminated, truncated_only;                   /* counters 0 and 1 of ModularEvaluator */
+  uint64_t last_reward_positive, last_reward_negative;   /* the win and loss of Evaluator.evaluate */
+  uint64_t negative_discounted;                          /* counter 3 of ModularEvaluator */
+  uint64_t length_sum;
+  int32_t  length_min, length_max;                       /* INT32_MAX / 0 when episodes == 0 */
+  double   return_mean, return_std;                      /* 0 when episodes == 0 */
+  double   return_min, return_max;                       /* +INFINITY / -INFINITY when episodes == 0 */
+  double   discounted_mean, discounted_std;
+} PgtgEvalSummary;
+int pgtg_eval_step(pgtg_handle* h, const PgtgEval* a);
+int pgtg_eval_summary(pgtg_handle* h, const PgtgEval* a, PgtgEvalSummary* out_dev, void* workspace);
+int pgtg_eval_workspace_bytes(uint64_t n, uint64_t n_episodes, uint64_t* bytes);
 /* Re-emit the observation of every env into the bound outputs (after set_agent/add_car). */
 int pgtg_observe(pgtg_handle* h);
 /* Per-env uint64 digest of the car list into out_dev[N] (device; parity tests: the car term of

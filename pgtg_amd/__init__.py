@@ -5,6 +5,7 @@ Drop-in for the reference's hot path (Inuri04/pgtg `PGTGEnv.step/reset`, registe
   PGTGEnv     -- single-env Gymnasium-style facade with the reference's constructor and returns
   Snapshot    -- single envs of a batch saved, restored and forked on the device (PGTGVecEnv.snapshot)
   Rollout     -- PPO rollout buffer on the device with a fused GAE kernel (PGTGVecEnv.rollout)
+  Evaluation  -- policy evaluation on the device with SB3's per-env episode quotas (PGTGVecEnv.evaluation)
 """
 from .config import EnvSpec, make_spec  # noqa: F401
 
@@ -21,6 +22,9 @@ def __getattr__(name):
     if name in ("DevicePolicy", "MlpPolicyReference", "DeviceAdam"):  # (SB3's MlpPolicy: k_policy, its yardstick, the optimiser step)
         from . import policy
         return getattr(policy, name)
+    if name in ("Evaluation", "evaluate_policy", "evaluate_reference"):  # (quota-aware evaluation: k_eval)
+        from . import evaluate
+        return getattr(evaluate, name)
     if name == "PGTGEnv":
         from .env import PGTGEnv
         return PGTGEnv

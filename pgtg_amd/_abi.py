@@ -34,6 +34,7 @@ EXPORTED = [
     "pgtg_timing_read", "pgtg_measure_hbm", "pgtg_state_size", "pgtg_dump_state", "pgtg_load_state",
     "pgtg_set_to_state", "pgtg_car_digest", "pgtg_get_queue_maps", "pgtg_get_queue_overflow", "pgtg_set_flat_outputs", "pgtg_set_flat_scalars",
     "pgtg_set_episode_stats", "pgtg_episode_summary", "pgtg_gae", "pgtg_flatten",
+    "pgtg_eval_step", "pgtg_eval_summary", "pgtg_eval_workspace_bytes",
     "pgtg_policy", "pgtg_policy_pack", "pgtg_policy_packed_bytes", "pgtg_policy_chunk",
     "pgtg_ppo_workspace_bytes", "pgtg_ppo_grad",
     "pgtg_ppo_step_workspace_bytes", "pgtg_ppo_step", "pgtg_ppo_adv_stats",
@@ -102,6 +103,25 @@ class PgtgGae(C.Structure):
     _fields_ = [("n", C.c_uint64), ("steps", C.c_uint64), ("gamma", C.c_double), ("gae_lambda", C.c_double)] + [
         (n, C.c_void_p) for n in ("rewards", "values", "dones", "truncated_only", "terminal_values", "last_values",
                                   "advantages", "returns")]
+
+
+EVAL_STATE_FIELDS = ("ret", "disc", "g", "len", "cnt")
+EVAL_RECORD_FIELDS = ("rec_return", "rec_discounted", "rec_length", "rec_last_reward", "rec_end_step", "rec_flags")
+
+
+class PgtgEval(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("n_episodes", C.c_uint64), ("step", C.c_uint64), ("gamma", C.c_double)] + [
+        (n, C.c_void_p) for n in ("reward", "terminated", "truncated") + EVAL_STATE_FIELDS + EVAL_RECORD_FIELDS
+        + ("open_rows",)]
+
+
+class PgtgEvalSummary(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("episodes", "open_envs", "terminated", "truncated_only",
+                                          "last_reward_positive", "last_reward_negative", "negative_discounted",
+                                          "length_sum")] + [
+        ("length_min", C.c_int32), ("length_max", C.c_int32)] + [
+        (n, C.c_double) for n in ("return_mean", "return_std", "return_min", "return_max", "discounted_mean",
+                                  "discounted_std")]
 
 
 PGTG_POLICY_SAMPLE, PGTG_POLICY_ARGMAX, PGTG_POLICY_VALUE_ONLY = 0, 1, 2
@@ -188,6 +208,9 @@ def lib():
         "pgtg_set_episode_stats": ([vp, vp, vp], C.c_int),
         "pgtg_episode_summary": ([vp, C.POINTER(PgtgEpisodeSummary), i32], C.c_int),
         "pgtg_gae": ([vp, C.POINTER(PgtgGae)], C.c_int),
+        "pgtg_eval_step": ([vp, C.POINTER(PgtgEval)], C.c_int),
+        "pgtg_eval_summary": ([vp, C.POINTER(PgtgEval), vp, vp], C.c_int),
+        "pgtg_eval_workspace_bytes": ([u64, u64, C.POINTER(u64)], C.c_int),
         "pgtg_policy": ([vp, C.POINTER(PgtgPolicy)], C.c_int),
         "pgtg_policy_pack": ([vp, C.POINTER(PgtgPolicyWeights), vp], C.c_int),
         "pgtg_policy_packed_bytes": ([u64, C.POINTER(u64)], C.c_int),

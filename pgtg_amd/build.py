@@ -8,7 +8,8 @@ import sys
 PKG = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(PKG, "csrc", "pgtg_env.hip")
 DEPS = [SRC, os.path.join(PKG, "csrc", "pgtg_device.h"), os.path.join(PKG, "csrc", "pgtg_tables.h"),
-        os.path.join(PKG, "csrc", "pgtg_episode.h"), os.path.join(PKG, "csrc", "pgtg_snapshot.h"),
+        os.path.join(PKG, "csrc", "pgtg_episode.h"), os.path.join(PKG, "csrc", "pgtg_eval.h"),
+        os.path.join(PKG, "csrc", "pgtg_snapshot.h"),
         os.path.join(PKG, "csrc", "pgtg_rollout.h"), os.path.join(PKG, "csrc", "pgtg_policy.h"),
         os.path.join(PKG, "csrc", "pgtg_ppo.h"), os.path.join(PKG, "csrc", "pgtg_ppo_step.h"),
         os.path.join(os.path.dirname(PKG), "include", "pgtg.h")]

@@ -27,6 +27,7 @@
 
 #include "pgtg_device.h"
 #include "pgtg_episode.h"
+#include "pgtg_eval.h"
 #include "pgtg_rollout.h"
 #include "pgtg_policy.h"
 #include "pgtg_ppo.h"
@@ -6441,6 +6442,61 @@ int pgtg_gae(pgtg_handle* h, const PgtgGae* a) {
   HIPCHK(h, hipSetDevice(h->device));
   if (g.tonly) hipLaunchKernelGGL(k_gae<true>, dim3((unsigned)grid), dim3(kGaeBlock), 0, h->stream, g);
   else hipLaunchKernelGGL(k_gae<false>, dim3((unsigned)grid), dim3(kGaeBlock), 0, h->stream, g);
+  HIPCHK(h, hipGetLastError());
+  return PGTG_OK;
+}
+
+// Quota-aware evaluation (pgtg_eval.h).  What both entry points check before they launch; 0 = fine.
+static int eval_check(pgtg_handle* h, const PgtgEval* a, const char* who, bool step) {
+  const std::string w(who);
+  if (!a) return fail(h, PGTG_E_INVALID, w + ": no arguments");
+  if (a->n != h->n) return fail(h, PGTG_E_INVALID, w + ": n must be the handle's env count");
+  if (a->n_episodes == 0) return fail(h, PGTG_E_INVALID, w + ": n_episodes must be at least 1");
+  if (!(a->gamma >= 0.0 && a->gamma <= 1.0)) return fail(h, PGTG_E_INVALID, w + ": gamma must be in [0, 1]");
+  if (!a->cnt || !a->rec_return || !a->rec_discounted || !a->rec_length || !a->rec_last_reward || !a->rec_end_step ||
+      !a->rec_flags)
+    return fail(h, PGTG_E_INVALID, w + ": cnt and the six record arrays are required");
+  if (step && (!a->reward || !a->terminated || !a->truncated || !a->ret || !a->disc || !a->g || !a->len || !a->open_rows))
+    return fail(h, PGTG_E_INVALID, w + ": reward, terminated, truncated, ret, disc, g, len and open_rows are required");
+  const uint64_t q = a->n_episodes / a->n + (a->n_episodes % a->n ? 1 : 0);
+  if (a->step > 0x7fffffffull || q > 0x7fffffffull || q > (1ull << 60) / a->n)
+    return fail(h, PGTG_E_INVALID, w + ": step, or the episode slots per env, is too large");
+  return 0;
+}
+
+int pgtg_eval_workspace_bytes(uint64_t n, uint64_t n_episodes, uint64_t* bytes) {
+  (void)n_episodes;  // (the partials are per 256 envs whatever the quotas)
+  if (!bytes || n == 0 || n > (1ull << 40)) return PGTG_E_INVALID;
+  *bytes = (n + kEvalBlock - 1) / kEvalBlock * sizeof(EvalPartial);
+  return PGTG_OK;
+}
+
+int pgtg_eval_step(pgtg_handle* h, const PgtgEval* a) {
+  if (!h) return PGTG_E_INVALID;
+  if (int rc = eval_check(h, a, "pgtg_eval_step", true)) return rc;
+  const uint64_t grid = (a->n + kEvalBlock - 1) / kEvalBlock;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_eval, dim3((unsigned)grid), dim3(kEvalBlock), 0, h->stream, *a);
+  HIPCHK(h, hipGetLastError());
+  return PGTG_OK;
+}
+
+int pgtg_eval_summary(pgtg_handle* h, const PgtgEval* a, PgtgEvalSummary* out_dev, void* workspace) {
+  if (!h) return PGTG_E_INVALID;
+  if (int rc = eval_check(h, a, "pgtg_eval_summary", false)) return rc;
+  if (!out_dev || !workspace || ((uintptr_t)workspace & 7) || ((uintptr_t)out_dev & 7))
+    return fail(h, PGTG_E_INVALID, "pgtg_eval_summary: out_dev and workspace are required, 8-byte aligned");
+  EvalReduceArgs r;
+  r.ev = *a;
+  r.rows = reinterpret_cast<EvalPartial*>(workspace);
+  r.out = out_dev;
+  r.n_rows = (a->n + kEvalBlock - 1) / kEvalBlock;
+  HIPCHK(h, hipSetDevice(h->device));
+  for (int pass = 0; pass < 2; pass++) {  // the means, then the squared deviations about them
+    r.pass = pass;
+    hipLaunchKernelGGL(k_eval_reduce, dim3((unsigned)r.n_rows), dim3(kEvalBlock), 0, h->stream, r);
+    hipLaunchKernelGGL(k_eval_final, dim3(1), dim3(kEvalBlock), 0, h->stream, r);
+  }
   HIPCHK(h, hipGetLastError());
   return PGTG_OK;
 }

@@ -586,6 +586,15 @@ class PGTGVecEnv:
         from .rollout import Rollout
         return Rollout(self, n_steps, gamma, gae_lambda, obs_dtype)
 
+    # -- policy evaluation on the device (ModularEvaluator.evaluate, pgtg/evaluator.py:284-339) --------
+    def evaluation(self, n_episodes: int, gamma: float = 0.99):
+        """An Evaluation (pgtg_amd/evaluate.py) of n_episodes episodes over this batch under SB3's per-env
+        quotas: every step ends with the HIP kernel k_eval, run(policy) is the whole loop.  Needs
+        autoreset=True and a flattenable observation (ValueError otherwise).  While it is active, the
+        Evaluation owns this handle's flat bindings (set_flat_outputs / set_flat_scalars)."""
+        from .evaluate import Evaluation
+        return Evaluation(self, n_episodes, gamma)
+
     def _bound_tensors(self) -> list:
         """Every tensor a step launch writes: the outputs and whatever else is bound."""
         ts = [self.obs_map, self.position, self.velocity, self.reward, self.terminated, self.truncated, self.braking,
