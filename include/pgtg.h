@@ -133,6 +133,10 @@ typedef struct {
   int32_t tune_fault;                  /* tests of the error paths: bit 0 clears the path walk's north
                                           mask on maps whose tile 0 keeps its east exit (inconsistent masks ->
                                           PGTG_E_DEVICE for those envs, the launch finishes) */
+  int32_t tune_step_ticks;             /* pgtg_step_many on a k_envq handle: ticks per launch at most (0: 64,
+                                          1 a launch per tick) */
+  int32_t tune_queue_grid;             /* k_envq's persistent grid at most (tests: more rounds of blocks per
+                                          workgroup at small batches) */
 } PgtgConfig;
 
 /* Output buffers (device pointers, caller-owned, contiguous).  NULL = not produced. */
@@ -548,6 +552,9 @@ int pgtg_get_counters(pgtg_handle* h, uint64_t* env_steps, uint64_t* episodes);
  * waves; 0 for handles without the queue): a window's delta beside its episode delta shows that the
  * maps the episodes consumed were generated in the window.  Synchronises. */
 int pgtg_get_queue_maps(pgtg_handle* h, uint64_t* maps);
+/* Step-kernel launches since create: one per pgtg_step, and per pgtg_step_many one per tick or, where it runs
+ * several ticks in a launch, one per such launch.  Host counter, no synchronisation. */
+int pgtg_get_step_launches(pgtg_handle* h, uint64_t* launches);
 /* Map-queue refill requests served from the overflow lists since create (step launches of one round
  * of workgroups list at most 64 requests per workgroup; the rest go to lists shared by residue mod 8
  * and are served by other workgroups' helper waves in the next launch).  Synchronises. */

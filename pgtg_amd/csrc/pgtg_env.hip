@@ -120,11 +120,21 @@ __device__ unsigned long long g_stamps[1 << 21];
       g_stamps[(1 << 20) | ((((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 8 + (k))) & ((1 << 20) - 1))] = \
           __builtin_amdgcn_s_memrealtime();                                                           \
   } while (0)
+// wall-clock end of tick t (< 256) of a launch of k_envq<BIG, true>, wave 0 of workgroups 0..2047: row blockIdx.x
+// of 256 stamps from word 1 << 19 (above STAMP's rows, below STAMPR's)
+#define STAMPT(t)                                                                                              \
+  do {                                                                                                         \
+    if (threadIdx.x == 0 && blockIdx.x < 2048u && (t) < 256u)                                                  \
+      g_stamps[(1 << 19) + blockIdx.x * 256u + (t)] = __builtin_amdgcn_s_memrealtime();                        \
+  } while (0)
 #else
 #define STAMP(k) \
   do {           \
   } while (0)
 #define STAMPR(k) \
+  do {            \
+  } while (0)
+#define STAMPT(t) \
   do {            \
   } while (0)
 #endif
@@ -2860,6 +2870,7 @@ constexpr int kViewDw = 8;       // k_envq with <= 32 envs: an env's view words 
 // its last phase (the observation write) and no barrier separates that from the next block's clear, so the
 // next block clears and marks the other one (whose readers are two barriers behind).
 constexpr int kObsMasks = 2;
+constexpr uint32_t kStepTicks = 64;  // ticks per launch of k_envq<BIG, true> at most (pgtg_step_many)
 constexpr uint32_t kQselFull = 8u;  // k_envq's qsel: write every observation line (the buffer is not current)
 
 // a ring entry's spawn tag (its last word): the spawn counter it was generated for, inverted so that
@@ -3455,6 +3466,20 @@ __device__ __forceinline__ void sub_barrier(uint32_t* ctr, uint32_t target) {
 // after the step), so that the plan's address does not wait for a load of its own at staging.
 // (One shared request list instead: 497 vs 456 us per 1 048 576-env launch, its counter a hot spot on
 // every env wave's path; static blocks blockIdx.x + k * gridDim.x: 455 us against the counter's 424.)
+// FUSED (pgtg_step_many): `ticks` ticks in one launch, tick k reading its actions at actions + k *
+// act_stride.  Workgroup w owns blocks w, w + gridDim.x, ... for the whole launch and steps them all for
+// one tick, then for the next: no block counter, and nothing passes between workgroups -- an env's
+// record, ring, qstate byte and outputs, and a workgroup's request lists, are written and read by waves
+// of that one workgroup -- so no workgroup waits for another, and a slow one is waited for once per
+// launch instead of once per tick.  Inside the workgroup two LDS counters hand the lists and the ring
+// entries over (rdone, fdone), each with a workgroup-scope release before and acquire after: the
+// workgroup runs on one CU, whose vector L1 all its waves share and write through, and no other
+// workgroup reads any of it before the launch ends.  Progress: the helper serving tick t waits only for
+// the env and writer waves' arrivals at the end of tick t - 1; those waves, in tick t, wait only for the
+// helper's fills of tick t - 1, which waited for tick t - 2: every wait is for a strictly earlier tick.
+// The launch before must have left request lists of the same ownership (pgtg_handle::q_static), since an
+// entry the helper makes in the first tick may be taken in the second.  The results are those of
+// `ticks` launches; every tick makes every store a launch of its own would make.
 // The map-queue step's observation images.  With <= 32 envs per workgroup they all sit in wave 0
 // and most of its lanes are idle, so each env's image is built by a group of G = 192 / E lanes of
 // the three non-helper waves (the env wave publishes its envs' views in LDS): lane e of wave 0 (the
@@ -3543,10 +3568,10 @@ __device__ __forceinline__ QueueMeta ring_take(const DevCfg& c, const DevState& 
   return QueueMeta(meta);
 }
 
-template <bool BIG>
+template <bool BIG, bool FUSED = false>
 __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ cfg, const Tables* __restrict__ gtab,
                                                     DevState S, const uint8_t* __restrict__ actions, PgtgOutputs out,
-                                                    Lds L, uint32_t qsel) {
+                                                    Lds L, uint32_t qsel, uint32_t ticks, uint64_t act_stride) {
   extern __shared__ uint32_t lds[];
   const DevCfg& c = *cfg;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -3557,7 +3582,8 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
   const bool env_wave = wave < env_waves;
   // refill requests: this launch's into list qsel & 3 (buffer qsel >> 2), the previous launch's from
   // list (qsel + 2) % 3 (the other buffer); the third list's counters are cleared for the next launch
-  const uint32_t par = (qsel >> 2) & 1u;
+  // (FUSED: the parity flips at every tick, as the host's qsel sequence does from launch to launch)
+  uint32_t par = (qsel >> 2) & 1u;
   const uint64_t nblk = (S.n + (uint64_t)L.envs - 1) / (uint64_t)L.envs;
   const uint64_t cap = queue_req_cap(nblk, gridDim.x, L.envs);  // requests per workgroup and launch
   uint2* req_new = S.qreq + ((uint64_t)par * gridDim.x + blockIdx.x) * cap;
@@ -3565,7 +3591,8 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
   // One round of blocks (every workgroup one block): a helper's time is on the launch's path, so a
   // workgroup lists at most kQueueLanes requests (one batch) and appends the rest to an overflow
   // list shared by the workgroups of its residue mod 8, whose helpers fill their spare lanes from it.
-  const bool one_round = nblk <= gridDim.x;
+  // (Never FUSED: the host runs several ticks per launch only on grids of more than one round.)
+  const bool one_round = !FUSED && nblk <= gridDim.x;
   const uint32_t ox = blockIdx.x & 7u, set_new = qsel & 3u, set_old = (set_new + 2u) % 3u;
   const uint64_t ocap = ((gridDim.x + 7u) / 8u) * (uint64_t)L.envs;  // an overflow list's capacity
   // the helper's list length and first requests, issued before the tables are staged
@@ -3589,18 +3616,30 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
   // Only the observation lines of envs whose observation changed are written (obs_key; an env that
   // finished, or failed, counts as changed): the others' bytes are in out.obs already, which the host
   // vouches for by leaving kQselFull clear.  Other configurations write every line.
+  // (FUSED: the ticks after the first find the buffer current -- the tick before wrote what changed.)
   const bool delta = lm && out.obs && obs_key_ok(c) && !(qsel & kQselFull) && kObsMasks * L.lm_words <= L.scratch_dw * L.envs;
   uint32_t* const om0 = lds + L.envs * pdw;  // (the hand-over words: see kObsMasks)
   uint32_t* om = delta ? om0 : nullptr;  // this block's changed-observation lines (alternating)
-  uint32_t* qn = ctr + 1;  // this launch's requests so far
+  uint32_t* qn = ctr + 1;  // this launch's (FUSED: this tick's) requests so far
   uint32_t* nxt = ctr + 2;  // the next block
+  // FUSED, the hand-offs between the env and writer waves and the helper, counters that only grow:
+  // rdone counts those waves' arrivals at a tick's end (its requests and their count are stored),
+  // fdone the ticks whose fills the helper has stored
+  uint32_t* rdone = ctr + 3;
+  uint32_t* fdone = ctr + 4;
   // blocks after the first: taken from a counter (three, rotating: this launch's, the next one's
-  // cleared here), one block ahead
+  // cleared here), one block ahead.  FUSED takes none (a workgroup owns blocks blockIdx.x + k * gridDim.x
+  // for the whole launch) and leaves all three cleared for whichever launch follows.
   uint32_t* bctr = S.qctr + kQctrBlocks;
-  if (blockIdx.x == 0 && tid == 0) bctr[((qsel & 3u) + 1u) % 3u] = 0u;
+  if (FUSED) {
+    if (blockIdx.x == 0 && tid < 3) bctr[tid] = 0u;
+  } else if (blockIdx.x == 0 && tid == 0) {
+    bctr[((qsel & 3u) + 1u) % 3u] = 0u;
+  }
   if (tid == 0) {
     *ctr = 0u;
     *qn = 0u;
+    if (FUSED) *rdone = *fdone = 0u;
   }
   lds_barrier();  // tables, counters
   // The qstate byte is wanted in its register before a block's staging begins.  Loads and stores retire
@@ -3613,57 +3652,73 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
     STAMP(1);
     // the helper: the previous launch's requests, kQueueLanes at a time, until none is left
     uint16_t* gplan = reinterpret_cast<uint16_t*>(lds + L.gen_off + lane * pdw);
-    uint32_t made = 0, ovs = 0;  // maps generated, of them overflow requests
-    if (!ABLATE(L, 1)) {
-      // one round: this helper's share of its residue's overflow list -- as many as its spare lanes,
-      // after those of the workgroups before it (a prefix sum over their list lengths, no atomics:
-      // 128 helpers claiming from one counter waited 7 us for it); what outgrows every spare lane
-      // follows in whole batches by workgroup order
-      const uint2* ovf = S.qovf + ((uint64_t)(par ^ 1u) * 8u + ox) * ocap;
-      uint32_t ob = 0, on = 0, olen = 0, tot = 0;
-      const uint32_t nj = (gridDim.x - ox + 7u) / 8u, jme = blockIdx.x / 8u;
-      if (one_round) {
-        olen = S.qctr[kQctrOvfLen + set_old * 8u + ox];
-        if (olen > 0) {
-          uint32_t pre = 0;
-          for (uint32_t j0 = 0; j0 < nj; j0 += kQueueLanes) {
-            const uint32_t j = j0 + (uint32_t)lane;
-            const uint32_t sp = j < nj ? kQueueLanes - min(S.qctr[(par ^ 1u) * gridDim.x + ox + 8u * j], (uint32_t)kQueueLanes) : 0u;
-            pre += wave_sum(j < jme ? sp : 0u);
-            tot += wave_sum(sp);
+    for (uint32_t tick = 0;;) {  // (FUSED: tick after tick, each one serving the list of the tick before)
+      uint32_t made = 0, ovs = 0;  // maps generated, of them overflow requests
+      if (!ABLATE(L, 1)) {
+        // one round: this helper's share of its residue's overflow list -- as many as its spare lanes,
+        // after those of the workgroups before it (a prefix sum over their list lengths, no atomics:
+        // 128 helpers claiming from one counter waited 7 us for it); what outgrows every spare lane
+        // follows in whole batches by workgroup order
+        const uint2* ovf = S.qovf + ((uint64_t)(par ^ 1u) * 8u + ox) * ocap;
+        uint32_t ob = 0, on = 0, olen = 0, tot = 0;
+        const uint32_t nj = (gridDim.x - ox + 7u) / 8u, jme = blockIdx.x / 8u;
+        if (one_round) {
+          olen = S.qctr[kQctrOvfLen + set_old * 8u + ox];
+          if (olen > 0) {
+            uint32_t pre = 0;
+            for (uint32_t j0 = 0; j0 < nj; j0 += kQueueLanes) {
+              const uint32_t j = j0 + (uint32_t)lane;
+              const uint32_t sp = j < nj ? kQueueLanes - min(S.qctr[(par ^ 1u) * gridDim.x + ox + 8u * j], (uint32_t)kQueueLanes) : 0u;
+              pre += wave_sum(j < jme ? sp : 0u);
+              tot += wave_sum(sp);
+            }
+            on = olen > pre ? min(olen - pre, kQueueLanes - min(cnt, (uint32_t)kQueueLanes)) : 0u;
+            ob = pre;
           }
-          on = olen > pre ? min(olen - pre, kQueueLanes - min(cnt, (uint32_t)kQueueLanes)) : 0u;
-          ob = pre;
+        }
+        for (uint32_t base = 0;; base += kQueueLanes) {  // the workgroup's own requests (and the spare lanes')
+          const uint32_t own = base < cnt ? min((uint32_t)kQueueLanes, cnt - base) : 0u;
+          const uint32_t oth = base == 0 ? on : 0u;
+          if (own + oth == 0) break;
+          made += own + oth;
+          ovs += oth;
+          if ((uint32_t)lane < own + oth) {
+            const uint2 r = (uint32_t)lane >= own ? ovf[ob + (lane - own)] : base == 0 ? r0 : req_old[base + lane];
+            const uint64_t ie = r.x >> 2;
+            gen_queue_entry<BIG>(c, S, ie, r.y, gplan, pdw, S.qbuf + (ie * kQueueDepth + queue_slot(r.x)) * (uint64_t)c.qrec_dw,
+                                 ABLATE(L, 16), false);
+          }
+          if (base + kQueueLanes >= cnt) break;
+        }
+        for (uint64_t st0 = tot + (uint64_t)jme * kQueueLanes; st0 < olen; st0 += (uint64_t)nj * kQueueLanes) {
+          const uint32_t m = (uint32_t)min((uint64_t)kQueueLanes, olen - st0);
+          made += m;
+          ovs += m;
+          if ((uint32_t)lane < m) {
+            const uint2 r = ovf[st0 + lane];
+            const uint64_t ie = r.x >> 2;
+            gen_queue_entry<BIG>(c, S, ie, r.y, gplan, pdw, S.qbuf + (ie * kQueueDepth + queue_slot(r.x)) * (uint64_t)c.qrec_dw,
+                                 ABLATE(L, 16), false);
+          }
         }
       }
-      for (uint32_t base = 0;; base += kQueueLanes) {  // the workgroup's own requests (and the spare lanes')
-        const uint32_t own = base < cnt ? min((uint32_t)kQueueLanes, cnt - base) : 0u;
-        const uint32_t oth = base == 0 ? on : 0u;
-        if (own + oth == 0) break;
-        made += own + oth;
-        ovs += oth;
-        if ((uint32_t)lane < own + oth) {
-          const uint2 r = (uint32_t)lane >= own ? ovf[ob + (lane - own)] : base == 0 ? r0 : req_old[base + lane];
-          const uint64_t ie = r.x >> 2;
-          gen_queue_entry<BIG>(c, S, ie, r.y, gplan, pdw, S.qbuf + (ie * kQueueDepth + queue_slot(r.x)) * (uint64_t)c.qrec_dw,
-                               ABLATE(L, 16), false);
-        }
-        if (base + kQueueLanes >= cnt) break;
-      }
-      for (uint64_t st0 = tot + (uint64_t)jme * kQueueLanes; st0 < olen; st0 += (uint64_t)nj * kQueueLanes) {
-        const uint32_t m = (uint32_t)min((uint64_t)kQueueLanes, olen - st0);
-        made += m;
-        ovs += m;
-        if ((uint32_t)lane < m) {
-          const uint2 r = ovf[st0 + lane];
-          const uint64_t ie = r.x >> 2;
-          gen_queue_entry<BIG>(c, S, ie, r.y, gplan, pdw, S.qbuf + (ie * kQueueDepth + queue_slot(r.x)) * (uint64_t)c.qrec_dw,
-                               ABLATE(L, 16), false);
-        }
-      }
+      if (lane == 0 && made) atomicAdd(&S.counters[2], (unsigned long long)made);  // maps generated
+      if (lane == 0 && ovs) atomicAdd(&S.counters[3], (unsigned long long)ovs);  // overflow requests served
+      if (!FUSED || ++tick == ticks) break;
+      // FUSED: this tick's fills are stored (the env waves of the next tick wait for that before they take a
+      // ring head) ...
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      if (lane == 0) __hip_atomic_store(fdone, tick, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      // ... then the next list: every env and writer wave has arrived at the end of tick `tick - 1`, with
+      // its requests and their count stored.  The helper waits for nothing later than the tick it serves.
+      while (__hip_atomic_load(rdone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < tick * (uint32_t)(kBlock / 64 - 1))
+        __builtin_amdgcn_s_sleep(4);
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      par ^= 1u;
+      req_old = S.qreq + ((uint64_t)(par ^ 1u) * gridDim.x + blockIdx.x) * cap;
+      cnt = S.qctr[(par ^ 1u) * gridDim.x + blockIdx.x];
+      r0 = req_old[lane];
     }
-    if (lane == 0 && made) atomicAdd(&S.counters[2], (unsigned long long)made);  // maps generated
-    if (lane == 0 && ovs) atomicAdd(&S.counters[3], (unsigned long long)ovs);  // overflow requests served
     STAMP(7);
     STAMPR(3);
     return;
@@ -3673,10 +3728,17 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
   const int np = kBlock / 64 - 1;  // participating waves
   const int nthr = np * 64;
   uint32_t bar = 0;  // running sub_barrier target
+  uint32_t tick = 0;  // (FUSED)
   for (uint64_t blk = blockIdx.x; blk < nblk;) {
     STAMP(0);
     uint32_t got = 0xffffffffu;
-    if (tid == 0 && nblk > gridDim.x && *qn + 2u * (uint32_t)L.envs <= cap) got = atomicAdd(&bctr[qsel & 3u], 1u);
+    if (!FUSED && tid == 0 && nblk > gridDim.x && *qn + 2u * (uint32_t)L.envs <= cap) got = atomicAdd(&bctr[qsel & 3u], 1u);
+    // FUSED: the workgroup's next block, or its first one again for the next tick; none after the last tick
+    // (computed where it is used, from values that are at hand anyway: held through the block it cost a spill)
+    const auto next_block = [&]() -> uint64_t {
+      const uint64_t b = blk + gridDim.x;
+      return b < nblk ? b : (tick + 1u < ticks ? (uint64_t)blockIdx.x : nblk);
+    };
     // the per-lane values derive from an opaque copy of the lane id, block by block: hoisted out of
     // the loop, they and what the compiler derives from them would hold registers through every
     // block (the env waves spilled at 128 VGPRs)
@@ -3697,7 +3759,7 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
     int act = 0;
     if (live) {
       v = rec_load(S.rec, i);
-      act = actions[i];  // issued with the staging loads, not on the step's chain
+      act = actions[i];  // issued with the staging loads, not on the step's chain (FUSED: this tick's row)
       stage_plan<BIG>(reinterpret_cast<const uint16_t*>(ring_slot(queue_cur(qs))), c.plan_dq, plan_w, pdw);  // the cur slot
     }
     for (int k = rank; k < L.lm_words; k += nthr) lm[k] = 0u;
@@ -3744,7 +3806,14 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
     STAMP(29);
     // the next block's qstate bytes, a block ahead: their latency passes behind this block's writes,
     // and the next staging computes its plan address from a register
-    {
+    if (FUSED) {
+      // (an env's byte is written and read by the same lane, tick after tick: in order.  A workgroup
+      // that owns one block would read it here before this tick's store: it reads it behind that store.)
+      const uint64_t bn = next_block();
+      const uint64_t ni = bn * (uint64_t)L.envs + (uint64_t)slot;
+      qs_nx = 0;
+      if (bn != blk && bn < nblk && slot < L.envs && ni < S.n) qs_nx = S.qstate[ni];
+    } else {
       const uint32_t g = *nxt;
       const uint64_t ni = ((uint64_t)gridDim.x + g) * (uint64_t)L.envs + (uint64_t)slot;
       qs_nx = 0;
@@ -3754,6 +3823,13 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
       write_obs(out.final_obs + env0 * (uint64_t)c.obs_bytes, (uint32_t)nb, (uint32_t)c.obs_bytes, st, sel, rank, nthr, lm);
     STAMP(3);
     sub_barrier(ctr, bar += (uint32_t)np);  // terminal images written before they are rebuilt
+    if (FUSED && tick > 0 && blk == blockIdx.x) {
+      // the tick's first ring take: the helper has stored the fills it made during the tick before
+      // (requested two ticks back, the youngest entries a take can meet).  It started on them when
+      // this wave arrived at that tick's start, so the wait is for nothing later than this tick.
+      while (__hip_atomic_load(fdone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < tick) __builtin_amdgcn_s_sleep(1);
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
     const bool reset_now = my_sel != 0;
     const uint32_t k0 = v.spawn;
     const uint32_t qc = queue_cur(qs), qh = queue_head(qs);
@@ -3819,6 +3895,11 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
         S.qstate[i] = (uint8_t)(qh | queue_spare(qc, qh) << 2);
       }
     }
+    // FUSED, a workgroup that owns one block: its byte for the next tick, read back behind this tick's store
+    // (the same lane, the same address: in order; kept in a register from the take it cost a spill).  This
+    // load is younger than the wait above, which does not cover it: the byte is next used after the tick's
+    // boundary, at the staging of this block again, and waited for there.  On the last tick it is read for nothing.
+    if (FUSED && blk == blockIdx.x && blk + gridDim.x >= nblk && live) qs_nx = S.qstate[i];
     if (live) {
       rec_store(S.rec, i, v);
       S.err[i] = (uint8_t)(-err);
@@ -3839,10 +3920,35 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
       write_obs(out.obs + env0 * (uint64_t)c.obs_bytes, (uint32_t)nb, (uint32_t)c.obs_bytes, st, nullptr, rank, nthr, om);
     if (om) om = om == om0 ? om0 + L.lm_words : om0;  // (the other mask: see kObsMasks)
     if (tid == 0) atomicAdd(&S.counters[0], (unsigned long long)nb);
-    if (blk == blockIdx.x) stagger_record(L, S, t_start);
+    if (blk == blockIdx.x && (!FUSED || tick == 0)) stagger_record(L, S, t_start);
     STAMP(6);
-    blk = g == 0xffffffffu ? nblk : (uint64_t)gridDim.x + g;
-  }  STAMPR(3);
+    if (!FUSED) {
+      blk = g == 0xffffffffu ? nblk : (uint64_t)gridDim.x + g;
+      continue;
+    }
+    const uint64_t blk_nx = next_block();
+    if (blk + gridDim.x >= nblk) STAMPT(tick);  // (the tick's last block of this workgroup)
+    if (blk_nx > blk) {
+      blk = blk_nx;
+      continue;
+    }
+    // FUSED, the tick's last block (more ticks follow): its requests and their count are stored --
+    // tid 0's store above is behind the block's last barrier, hence behind every wave's requests --
+    // which each wave publishes to the helper as it arrives; none waits here.  The next tick writes the
+    // other list and counts from zero: nothing touches *qn before that tick's first barrier, and its
+    // first request follows the wait above the take, when the helper has read the list it then rewrites.
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    if (lane == 0) __hip_atomic_fetch_add(rdone, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (tid == 0) *qn = 0u;
+    tick++;
+    par ^= 1u;
+    actions += act_stride;
+    req_new = S.qreq + ((uint64_t)par * gridDim.x + blockIdx.x) * cap;
+    // (a first tick that wrote every line: the buffer is current now)
+    if (!om && lm && out.obs && obs_key_ok(c) && kObsMasks * L.lm_words <= L.scratch_dw * L.envs) om = om0;
+    blk = blk_nx;
+  }
+  STAMPR(3);
 }
 
 // Step launch with the map queue for grids of at most two rounds of workgroups (k_envb: the map
@@ -4700,6 +4806,13 @@ struct pgtg_handle {
   int q_block = -1;
   bool slot_plan = false;  // a k_envq handle: no S.plan, an env's plan is the cur slot of its ring
   int tune_queue_mode = 0;  // PgtgConfig.tune_queue_mode
+  int tune_queue_grid = 0;  // PgtgConfig.tune_queue_grid
+  // pgtg_step_many on a k_envq handle: ticks per launch of k_envq<BIG, true> at most (PgtgConfig.tune_step_ticks;
+  // 1: a launch per tick), and whether the pending request lists hold, per workgroup, only requests for
+  // envs of the blocks that workgroup owns in k_envq<BIG, true> (empty lists, or made by k_envq<BIG, true> itself)
+  uint32_t step_ticks = kStepTicks;
+  uint64_t step_kernels = 0;  // step-kernel launches so far, whatever their ticks (pgtg_get_step_launches)
+  bool q_static = false;
   // The bound obs buffer holds every env's current observation: set by a launch that wrote them all,
   // cleared by whatever changes an env's state, the output binding or the step kernel without rewriting
   // them.  k_envq then writes only the lines of the observations that changed (obs_key).
@@ -4724,8 +4837,8 @@ struct pgtg_handle {
 // Every step-kernel instance, once: its argument list (launch) and the name pgtg_step_kernel reports, alone
 // and with k_traffic behind it.  The SLOT instances of k_env (a k_envq handle: an env's plan is in its ring
 // slot) report as their counterparts with plan rows.  Two rows per family: BIG (maps of > 64 tiles), then not.
-enum StepArgs { ARGS_ENV, ARGS_ENVB, ARGS_ENVQ };
-enum StepFamily { ENV_TR_SLOT, ENV_SLOT, ENV_TR, ENVB, ENVQ, ENV, kStepFamilies };
+enum StepArgs { ARGS_ENV, ARGS_ENVB, ARGS_ENVQ, ARGS_ENVQ_MANY };
+enum StepFamily { ENV_TR_SLOT, ENV_SLOT, ENV_TR, ENVB, ENVQ, ENV, ENVQ_MANY, kStepFamilies };
 struct StepKernel {
   const void* fn;
   StepArgs args;
@@ -4745,6 +4858,8 @@ static const StepKernel kStepKernels[2 * kStepFamilies] = {
     STEP_ROW((k_envq<false>), ARGS_ENVQ, "pgtg::k_envq<false>"),
     STEP_ROW((k_env<false, true>), ARGS_ENV, "pgtg::k_env<false, true>"),
     STEP_ROW((k_env<false, false>), ARGS_ENV, "pgtg::k_env<false, false>"),
+    STEP_ROW((k_envq<true, true>), ARGS_ENVQ_MANY, "pgtg::k_envq<true, true>"),
+    STEP_ROW((k_envq<false, true>), ARGS_ENVQ_MANY, "pgtg::k_envq<false, true>"),
 };
 #undef STEP_ROW
 
@@ -5266,6 +5381,7 @@ static int choose_launch(pgtg_handle* h, bool allow_queue) {
     // (more, with the later ones waiting for a slot: 125 % of them 429 vs 424 us per 1 048 576-env
     // launch, 150 % 450 us)
     h->q_grid = std::max<uint64_t>(1, std::min(std::min(blocks, (uint64_t)h->L.stagger_wgs), (uint64_t)kMaxQueueGrid));
+    if (h->tune_queue_grid > 0) h->q_grid = std::min(h->q_grid, (uint64_t)h->tune_queue_grid);  // forced: more rounds
     // the map queue's step kernel, once per handle (its ring layout follows): k_envb for grids of at
     // most two rounds of workgroups, k_envq's persistent grid beyond
     if (h->q_block < 0 && h->L.queue)
@@ -5287,6 +5403,11 @@ static int create(pgtg_handle* h, const PgtgConfig* cfg) {
   h->tune_kt_cap = cfg->tune_kt_cap;
   h->tune_kt_wpc = cfg->tune_kt_wpc;
   h->tune_queue_mode = cfg->tune_queue_mode;
+  h->tune_queue_grid = cfg->tune_queue_grid;
+  if (cfg->tune_step_ticks > 0) h->step_ticks = (uint32_t)cfg->tune_step_ticks;
+#ifdef PGTG_TUNING
+  if (const char* e = getenv("PGTG_STEP_TICKS")) h->step_ticks = (uint32_t)std::max(1, atoi(e));
+#endif
   if (h->n == 0) return fail(h, PGTG_E_INVALID, "n_envs must be > 0");
   if (int rc = derive_cfg(h, *cfg, h->hcfg)) return rc;
   if (hipSetDevice(h->device) != hipSuccess) return fail(h, PGTG_E_DEVICE, "hipSetDevice failed");
@@ -5532,12 +5653,15 @@ static int launch(pgtg_handle* h, const uint8_t* actions, const uint8_t* mask, i
     HIPCHK(h, hipEventRecord(h->evpool[h->ev_used], h->stream));
   }
   const StepKernel& k = step_fn(h, mode);
+  if (mode == MODE_STEP) h->step_kernels++;
   const bool full = !h->obs_current;  // (k_envq) every observation line is written
   h->obs_current = false;                    // (until this launch and what follows it have gone out)
   uint32_t qsel = (uint32_t)(h->q_launch % 3) | (uint32_t)(h->q_launch & 1) << 2 | (full ? kQselFull : 0u);  // k_envq: its rotating lists
   void* args[] = {&h->dcfg, &h->dtab, &h->S, &actions, &mask, &h->out, &mode, &h->L, &h->tr_slot};
   void* bargs[] = {&h->dcfg, &h->dtab, &h->S, &actions, &h->out, &h->L};
-  void* qargs[] = {&h->dcfg, &h->dtab, &h->S, &actions, &h->out, &h->L, &qsel};
+  uint32_t one_tick = 1;
+  uint64_t no_stride = 0;
+  void* qargs[] = {&h->dcfg, &h->dtab, &h->S, &actions, &h->out, &h->L, &qsel, &one_tick, &no_stride};
   void** kargs = args;
   switch (k.args) {
     case ARGS_ENV: break;
@@ -5545,8 +5669,10 @@ static int launch(pgtg_handle* h, const uint8_t* actions, const uint8_t* mask, i
     case ARGS_ENVQ:  // the persistent grid
       kargs = qargs;
       h->q_launch++;
+      h->q_static = false;  // (blocks taken from the counter: a workgroup's list names any env)
       blocks = std::min(blocks, h->q_grid);
       break;
+    case ARGS_ENVQ_MANY: return fail(h, PGTG_E_INVALID, "k_envq<BIG, true> is launched by pgtg_step_many");
   }
   HIPCHK(h, hipLaunchKernel(k.fn, dim3((unsigned)blocks), dim3(kBlock), kargs, h->lds, h->stream));
   HIPCHK(h, hipGetLastError());
@@ -5580,6 +5706,7 @@ static int launch(pgtg_handle* h, const uint8_t* actions, const uint8_t* mask, i
 static int queue_fill(pgtg_handle* h) {
   if (!h->L.queue || !h->S.qbuf) return PGTG_OK;
   if (h->S.qctr) HIPCHK(h, hipMemsetAsync(h->S.qctr, 0, kQctrWords * sizeof(uint32_t), h->stream));
+  h->q_static = true;  // (no request pending)
 #ifdef PGTG_TUNING
   if (const char* e = getenv("PGTG_QFILL"))
     if (!atoi(e)) return PGTG_OK;
@@ -5631,10 +5758,53 @@ int pgtg_step(pgtg_handle* h, const uint8_t* actions_dev) {
   return launch(h, actions_dev, nullptr, MODE_STEP);
 }
 
+// pgtg_step_many may run several ticks per launch: a handle whose step kernel is the persistent k_envq
+// on a grid of more than one round (one round keeps its shared overflow lists, which pass requests
+// between workgroups), no per-launch timing and nothing that runs after every step launch.
+static bool step_many_fused(const pgtg_handle* h) {
+  if (h->step_ticks < 2 || h->timing > 0 || h->flat_dst || h->final_flat_dst || h->ep.out_ret) return false;
+  if (step_fn(h, MODE_STEP).args != ARGS_ENVQ) return false;
+  return (h->n + h->L.envs - 1) / h->L.envs > h->q_grid;
+}
+
+// `ticks` ticks of a k_envq handle in one launch of k_envq<BIG, true> (what launch() does for a step, for the
+// handles step_many_fused admits).  launch()'s k_traffic, flatten, episode-statistics and timing steps have no
+// place here: step_many_fused refuses the handles that need one, which the guard below repeats, so that a
+// later change to step_fn or to what follows a step launch fails loudly instead of skipping work.
+static int launch_many(pgtg_handle* h, const uint8_t* actions, uint64_t row_stride, uint32_t ticks) {
+  if (!step_many_fused(h) || h->hcfg.need_car || h->hcfg.n_rules > 0)
+    return fail(h, PGTG_E_INVALID, "launch_many on a handle that needs a launch per tick");
+  HIPCHK(h, hipSetDevice(h->device));
+  const StepKernel& k = kStepKernels[2 * ENVQ_MANY + (h->hcfg.nt > kSmallTiles ? 0 : 1)];
+  const bool full = !h->obs_current;  // (the first tick writes every observation line)
+  h->obs_current = false;
+  uint32_t qsel = (uint32_t)(h->q_launch % 3) | (uint32_t)(h->q_launch & 1) << 2 | (full ? kQselFull : 0u);
+  void* args[] = {&h->dcfg, &h->dtab, &h->S, &actions, &h->out, &h->L, &qsel, &ticks, &row_stride};
+  h->q_launch += ticks;  // (the lists rotate per tick inside the kernel, by the rule of launch())
+  h->step_kernels++;
+  h->q_static = true;
+  HIPCHK(h, hipLaunchKernel(k.fn, dim3((unsigned)h->q_grid), dim3(kBlock), args, h->lds, h->stream));
+  HIPCHK(h, hipGetLastError());
+  h->obs_current = h->out.obs != nullptr;
+  return PGTG_OK;
+}
+
 int pgtg_step_many(pgtg_handle* h, const uint8_t* actions_dev, uint64_t row_stride, uint64_t ticks) {
   if (!h || !actions_dev || row_stride < h->n) return PGTG_E_INVALID;
-  for (uint64_t k = 0; k < ticks; k++)
-    if (int rc = launch(h, actions_dev + k * row_stride, nullptr, MODE_STEP)) return rc;
+  if (ticks < 2 || !step_many_fused(h)) {
+    for (uint64_t k = 0; k < ticks; k++)
+      if (int rc = launch(h, actions_dev + k * row_stride, nullptr, MODE_STEP)) return rc;
+    return PGTG_OK;
+  }
+  // Launches of at most step_ticks ticks.  After a launch of k_envq, whose workgroups take blocks from a
+  // counter, a workgroup's list names envs of blocks that other workgroups own here, and their entries may
+  // be taken one tick after the helper makes them: that list is served by a launch of one tick, whose
+  // end every workgroup waits for as before.
+  for (uint64_t k = 0; k < ticks;) {
+    const uint32_t t = h->q_static ? (uint32_t)std::min<uint64_t>(ticks - k, h->step_ticks) : 1u;
+    if (int rc = launch_many(h, actions_dev + k * row_stride, row_stride, t)) return rc;
+    k += t;
+  }
   return PGTG_OK;
 }
 
@@ -6273,6 +6443,12 @@ int pgtg_get_counters(pgtg_handle* h, uint64_t* env_steps, uint64_t* episodes) {
   if (int rc = read_counters(h, c)) return rc;
   if (env_steps) *env_steps = c[0];
   if (episodes) *episodes = c[1];
+  return PGTG_OK;
+}
+
+int pgtg_get_step_launches(pgtg_handle* h, uint64_t* launches) {
+  if (!h || !launches) return PGTG_E_INVALID;
+  *launches = h->step_kernels;
   return PGTG_OK;
 }
 

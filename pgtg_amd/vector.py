@@ -688,6 +688,12 @@ class PGTGVecEnv:
         _check(self._lib.pgtg_get_queue_maps(self._h, C.byref(m)), self._h)
         return m.value
 
+    def step_launches(self) -> int:
+        """Step-kernel launches since create (step_many may run several ticks in one)."""
+        m = C.c_uint64()
+        _check(self._lib.pgtg_get_step_launches(self._h, C.byref(m)), self._h)
+        return m.value
+
     def queue_overflow(self) -> int:
         """Map-queue refill requests served from the one-round overflow lists since create."""
         m = C.c_uint64()

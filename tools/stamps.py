@@ -2,6 +2,10 @@
 
 Build: hipcc <pgtg_amd.build.FLAGS> -DPGTG_STAMPS -o pgtg_amd/libpgtg_hip_stamps.so pgtg_amd/csrc/pgtg_env.hip
 Usage: python tools/stamps.py [cfg2|cfg5|cfg3 ...]
+PGTG_STAMP_TICKS=T (<= 256): after the single steps, one pgtg_step_many call of 1 + T ticks, whose last launch is
+k_envq<BIG, true> with T ticks (given T <= the handle's ticks per launch), then the tick dimension: every
+workgroup's wall-clock end of every tick of that launch, split into what is the same workgroup tick after tick
+(systematic: the spread of the workgroups' mean tick durations) and what varies within a workgroup (random).
 Only waves holding env lanes are summarised; a sub-phase is averaged over the waves whose lane 0
 executed it in the last launch (its stamps lie inside that wave's launch window)."""
 import ctypes as C
@@ -46,6 +50,9 @@ for name in (sys.argv[1:] or ["cfg2", "cfg5"]):
         env.step_random(1, k)
         if os.environ.get("PGTG_STAMP_SYNC") == "1":
             torch.cuda.synchronize()
+    T = int(os.environ.get("PGTG_STAMP_TICKS", "0"))
+    if T:
+        env.step_many(env.random_actions(1 + T, 2))
     torch.cuda.synchronize()
     blocks = (N + E - 1) // E
     nw = blocks * 4
@@ -129,6 +136,28 @@ for name in (sys.argv[1:] or ["cfg2", "cfg5"]):
         print("  wall clock (10 ns ticks from the first wave's start; mean, p50, p90, max): wave starts", q(beg),
               "env-wave ends", q(end[ew]) if ew.any() else None, "helper ends", q(end[hw]) if hw.any() else None,
               "writer-wave ends", q(end[~ew & ~hw]) if (~ew & ~hw).any() else None, flush=True)
+    if T and not spread and okw.any():  # the tick dimension of the last launch (k_envq<BIG, true>, T ticks)
+        wgs = int(wid.max()) // 4 + 1
+        tt = buf[(1 << 19):(1 << 19) + 256 * wgs].reshape(wgs, 256)[:, :T].astype(np.int64)
+        beg0 = rt[0:4 * wgs:4, 2]  # wave 0's start
+        if (tt > 0).all():
+            ends = tt - t0
+            d = np.diff(np.concatenate([(beg0 - t0)[:, None], ends], axis=1), axis=1)[:, 1:]  # ticks 1.. (tick 0 holds the ramp)
+            m = d.mean(1)  # a workgroup's mean tick
+            half = (T - 1) // 2
+            r = np.corrcoef(d[:, :half].mean(1), d[:, half:].mean(1))[0, 1]
+            last = ends[:, -1]
+            xcd = [round(float(m[k::8].mean()) / 100, 2) for k in range(8)]
+            print(f"  ticks in the launch: {T}, workgroups {wgs}; us: mean tick {d.mean() / 100:.1f}; "
+                  f"systematic: std of the workgroups' mean tick {m.std() / 100:.2f}, slowest workgroup's mean "
+                  f"{(m.max() - m.mean()) / 100:.2f} above the average, p99 {(np.percentile(m, 99) - m.mean()) / 100:.2f}; "
+                  f"random: std of a tick within a workgroup {d.std(1).mean() / 100:.2f}; correlation of a workgroup's "
+                  f"mean over the first and the second half of the ticks {r:.2f}; mean tick by workgroup index mod 8 {xcd}",
+                  flush=True)
+            print(f"  launch end: last workgroup {last.max() / 100:.1f} us, average {last.mean() / 100:.1f}, "
+                  f"tail per tick {(last.max() - last.mean()) / 100 / T:.2f}; per tick, the last workgroup's end above "
+                  f"the average end: {[round(float(x) / 100, 1) for x in (ends.max(0) - ends.mean(0))[[0, T // 4, T // 2, T - 1]]]} "
+                  f"at ticks {[0, T // 4, T // 2, T - 1]}", flush=True)
     if not spread:  # k_envq env waves: the observation channel loop's split (slots 24, 25)
         okc = (st[:, 24] > 0) & (st[:, 24] < 1e7) & (st[:, 25] < 1e7)
         if okc.any():
