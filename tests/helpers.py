@@ -113,15 +113,78 @@ def has_traffic(meta: dict) -> bool:
     return float(meta["kwargs"].get("traffic_density", 0) or 0) > 0
 
 
+def _compare_tick(env, d: dict, spec, perm, ix, planted: bool, t: int, reset_map: dict, bad: list) -> None:
+    """The handle's outputs after tick t against the trajectory's, at the envs ix: mismatch strings appended
+    to bad.  (replay_vec's comparison of a step, whether the tick was a launch of its own or the last of a
+    pgtg_step_many call.)"""
+    import torch
+    meta, N = d["meta"], len(ix)
+    torch.cuda.synchronize()
+    m = env.obs_map.cpu().numpy()[ix][:, perm]
+    fm = env.final_map.cpu().numpy()[ix][:, perm]
+    pos, vel = env.position.cpu().numpy()[ix], env.velocity.cpu().numpy()[ix]
+    fpos, fvel = env.final_position.cpu().numpy()[ix], env.final_velocity.cpu().numpy()[ix]
+    rew, term = env.reward.cpu().numpy()[ix], env.terminated.cpu().numpy()[ix]
+    trunc = env.truncated.cpu().numpy()[ix]
+    cost = env.cost.cpu().numpy()[ix] if env.cost is not None else np.zeros(N)
+    brk = env.braking.cpu().numpy()[ix]
+    nsd = env.nsd.cpu().numpy()[ix] if env.nsd is not None else None
+    fnsd = env.final_nsd.cpu().numpy()[ix] if env.final_nsd is not None else None
+    check_cars = has_traffic(meta)
+    for i, b in enumerate(ix):
+        tag = f"env{i}@{b} t{t}" if planted else f"env{i} t{t}"
+        if check_cars:
+            dig = digest(env.cars(b))
+            want = d["reset_cars_dig"][reset_map[(t, i)]] if term[i] and (t, i) in reset_map else d["cars_dig"][t, i]
+            if dig != int(want):
+                bad.append(f"{tag} cars")
+        if bool(term[i]) != bool(d["terminated"][t, i]) or trunc[i]:
+            bad.append(f"{tag} terminated {term[i]} vs {d['terminated'][t, i]}")
+            continue
+        if bool(brk[i]) != bool(d["braking"][t, i]):
+            bad.append(f"{tag} braking {brk[i]} vs {d['braking'][t, i]}")
+        if "triggered" in d and int(brk[i]) != int(d["triggered"][t, i]):
+            bad.append(f"{tag} triggered rules {int(brk[i]):#04x} vs {int(d['triggered'][t, i]):#04x}")
+        if rew[i] != d["reward"][t, i] or cost[i] != d["cost"][t, i]:
+            bad.append(f"{tag} reward {rew[i]} vs {d['reward'][t, i]} cost {cost[i]} vs {d['cost'][t, i]}")
+        if term[i]:
+            if not np.array_equal(fm[i], d["obs"][t, i]):
+                bad.append(f"{tag} final obs")
+            if tuple(fpos[i]) != tuple(d["pos"][t, i]) or tuple(fvel[i]) != tuple(d["vel"][t, i]):
+                bad.append(f"{tag} final pos/vel")
+            if fnsd is not None and fnsd[i] != d["nsd"][t, i]:
+                bad.append(f"{tag} final nsd")
+            k = reset_map[(t, i)]
+            if not np.array_equal(m[i], d["reset_obs"][k]):
+                bad.append(f"{tag} autoreset obs")
+            if tuple(pos[i]) != tuple(d["reset_pos"][k]):
+                bad.append(f"{tag} autoreset pos")
+            if nsd is not None and nsd[i] != d["reset_nsd"][k]:
+                bad.append(f"{tag} autoreset nsd")
+        else:
+            if not np.array_equal(m[i], d["obs"][t, i]):
+                diff = [meta["keys"][c] for c in range(len(perm)) if not np.array_equal(m[i, c], d["obs"][t, i, c])]
+                bad.append(f"{tag} obs {diff}")
+            if tuple(pos[i]) != tuple(d["pos"][t, i]) or tuple(vel[i]) != tuple(d["vel"][t, i]):
+                bad.append(f"{tag} pos/vel {pos[i]} {vel[i]} vs {d['pos'][t, i]} {d['vel'][t, i]}")
+            if nsd is not None and nsd[i] != d["nsd"][t, i]:
+                bad.append(f"{tag} nsd {nsd[i]} vs {d['nsd'][t, i]}")
+        if len(bad) > 30:
+            return
+
+
 def replay_vec(d: dict, n_envs: int | None = None, steps: int | None = None, n_batch: int | None = None,
-               at=None, tune: dict | None = None, info: dict | None = None) -> list[str]:
+               at=None, tune: dict | None = None, info: dict | None = None, chunks=None) -> list[str]:
     """Replay a golden trajectory through the HIP vector env (auto-reset); mismatch strings.
 
     n_batch, at: plant the fixture's envs in a batch of n_batch envs, env j at batch index at[j].  The
     batch is reset with one seed per env: seed_base + j at at[j], a filler seed (fixed rng, far above
     every fixture's seeds) everywhere else; the fillers step with fixed random actions.  Every
     comparison is made at the planted indices.  tune: PGTGVecEnv's.  info (dict): gets "step_kernel"
-    and, after the last step, "errors" (error_count()[0])."""
+    and, after the last step, "errors" (error_count()[0]).
+    chunks (list of call lengths that sum to the steps): instead of a step per tick, one step_many call per
+    chunk over resident [len, batch] action tensors, the comparison made after the last tick of each call;
+    info also gets "calls", "step_launches" (the step-kernel launches the calls took) and "end_ticks"."""
     import torch
     from pgtg_amd.vector import PGTGVecEnv
     meta = d["meta"]
@@ -133,6 +196,9 @@ def replay_vec(d: dict, n_envs: int | None = None, steps: int | None = None, n_b
     ix = list(range(N)) if at is None else [int(b) for b in at][:N]
     B = N if n_batch is None else int(n_batch)
     assert len(ix) == N and len(set(ix)) == N and all(0 <= b < B for b in ix), (ix, N, B)
+    if chunks is not None:
+        chunks = [int(k) for k in chunks]
+        assert all(k >= 1 for k in chunks) and sum(chunks) == T, (chunks, T)
     env = PGTGVecEnv(B, spec=spec, autoreset=True, tune=tune)
     bad: list[str] = []
     try:
@@ -162,65 +228,32 @@ def replay_vec(d: dict, n_envs: int | None = None, steps: int | None = None, n_b
             if spec.next_subgoal and int(nsd[i]) != int(d["init_nsd"][i]):
                 bad.append(f"{tag} reset nsd")
         reset_map = {(int(t), int(i)): k for k, (t, i) in enumerate(d["reset_idx"])}
-        for t in range(T):
+
+        def actions(t):
             if planted:
                 a = filler[t].copy()
                 a[ix] = d["actions"][t, :N]
-            else:
-                a = d["actions"][t, :N].astype(np.uint8)
-            env.step(torch.as_tensor(a.astype(np.uint8)).cuda())
-            torch.cuda.synchronize()
-            m = env.obs_map.cpu().numpy()[ix][:, perm]
-            fm = env.final_map.cpu().numpy()[ix][:, perm]
-            pos, vel = env.position.cpu().numpy()[ix], env.velocity.cpu().numpy()[ix]
-            fpos, fvel = env.final_position.cpu().numpy()[ix], env.final_velocity.cpu().numpy()[ix]
-            rew, term = env.reward.cpu().numpy()[ix], env.terminated.cpu().numpy()[ix]
-            trunc = env.truncated.cpu().numpy()[ix]
-            cost = env.cost.cpu().numpy()[ix] if env.cost is not None else np.zeros(N)
-            brk = env.braking.cpu().numpy()[ix]
-            nsd = env.nsd.cpu().numpy()[ix] if env.nsd is not None else None
-            fnsd = env.final_nsd.cpu().numpy()[ix] if env.final_nsd is not None else None
-            check_cars = has_traffic(meta)
-            for i, b in enumerate(ix):
-                tag = f"env{i}@{b} t{t}" if planted else f"env{i} t{t}"
-                if check_cars:
-                    dig = digest(env.cars(b))
-                    want = d["reset_cars_dig"][reset_map[(t, i)]] if term[i] and (t, i) in reset_map else d["cars_dig"][t, i]
-                    if dig != int(want):
-                        bad.append(f"{tag} cars")
-                if bool(term[i]) != bool(d["terminated"][t, i]) or trunc[i]:
-                    bad.append(f"{tag} terminated {term[i]} vs {d['terminated'][t, i]}")
-                    continue
-                if bool(brk[i]) != bool(d["braking"][t, i]):
-                    bad.append(f"{tag} braking {brk[i]} vs {d['braking'][t, i]}")
-                if "triggered" in d and int(brk[i]) != int(d["triggered"][t, i]):
-                    bad.append(f"{tag} triggered rules {int(brk[i]):#04x} vs {int(d['triggered'][t, i]):#04x}")
-                if rew[i] != d["reward"][t, i] or cost[i] != d["cost"][t, i]:
-                    bad.append(f"{tag} reward {rew[i]} vs {d['reward'][t, i]} cost {cost[i]} vs {d['cost'][t, i]}")
-                if term[i]:
-                    if not np.array_equal(fm[i], d["obs"][t, i]):
-                        bad.append(f"{tag} final obs")
-                    if tuple(fpos[i]) != tuple(d["pos"][t, i]) or tuple(fvel[i]) != tuple(d["vel"][t, i]):
-                        bad.append(f"{tag} final pos/vel")
-                    if fnsd is not None and fnsd[i] != d["nsd"][t, i]:
-                        bad.append(f"{tag} final nsd")
-                    k = reset_map[(t, i)]
-                    if not np.array_equal(m[i], d["reset_obs"][k]):
-                        bad.append(f"{tag} autoreset obs")
-                    if tuple(pos[i]) != tuple(d["reset_pos"][k]):
-                        bad.append(f"{tag} autoreset pos")
-                    if nsd is not None and nsd[i] != d["reset_nsd"][k]:
-                        bad.append(f"{tag} autoreset nsd")
-                else:
-                    if not np.array_equal(m[i], d["obs"][t, i]):
-                        diff = [meta["keys"][c] for c in range(len(perm)) if not np.array_equal(m[i, c], d["obs"][t, i, c])]
-                        bad.append(f"{tag} obs {diff}")
-                    if tuple(pos[i]) != tuple(d["pos"][t, i]) or tuple(vel[i]) != tuple(d["vel"][t, i]):
-                        bad.append(f"{tag} pos/vel {pos[i]} {vel[i]} vs {d['pos'][t, i]} {d['vel'][t, i]}")
-                    if nsd is not None and nsd[i] != d["nsd"][t, i]:
-                        bad.append(f"{tag} nsd {nsd[i]} vs {d['nsd'][t, i]}")
+                return a
+            return d["actions"][t, :N].astype(np.uint8)
+
+        if chunks is None:
+            for t in range(T):
+                env.step(torch.as_tensor(actions(t).astype(np.uint8)).cuda())
+                _compare_tick(env, d, spec, perm, ix, planted, t, reset_map, bad)
                 if len(bad) > 30:
                     return bad
+        else:
+            acts = torch.as_tensor(np.stack([actions(t).astype(np.uint8) for t in range(T)])).cuda()
+            l0, t0, ends = env.step_launches(), 0, []
+            for k in chunks:
+                env.step_many(acts[t0:t0 + k])
+                t0 += k
+                ends.append(t0 - 1)
+                _compare_tick(env, d, spec, perm, ix, planted, t0 - 1, reset_map, bad)
+                if len(bad) > 30:
+                    return bad
+            if info is not None:
+                info.update(calls=len(chunks), step_launches=env.step_launches() - l0, end_ticks=ends)
         if info is not None:
             info["errors"] = int(env.error_count()[0])
     finally:

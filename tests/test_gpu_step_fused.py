@@ -22,18 +22,18 @@ N_SMALL = 16 * 70 + 5  # 71 blocks, the last one of 5 envs
 SPEC3 = dict(random_map_width=3, random_map_height=3)
 
 
-def _tune(grid, step_ticks=None):
-    t = dict(queue_mode=1, envs_per_block=16, queue_grid=grid)
+def _tune(grid, step_ticks=None, envs_per_block=16):
+    t = dict(queue_mode=1, envs_per_block=envs_per_block, queue_grid=grid)
     if step_ticks is not None:
         t["step_ticks"] = step_ticks
     return t
 
 
-def _pair(spec, n, grid, step_ticks=None, seed=11):
-    """(several ticks per launch, a launch per tick), both reset with the same seed"""
+def _pair(spec, n, grid, step_ticks=None, seed=11, envs_per_block=16, **kw):
+    """(several ticks per launch, a launch per tick), both reset with the same seed; kw: PGTGVecEnv's"""
     from pgtg_amd.vector import PGTGVecEnv
-    a = PGTGVecEnv(n, spec=spec, device=0, tune=_tune(grid, step_ticks))
-    b = PGTGVecEnv(n, spec=spec, device=0, tune=_tune(grid, 1))
+    a = PGTGVecEnv(n, spec=spec, device=0, tune=_tune(grid, step_ticks, envs_per_block), **kw)
+    b = PGTGVecEnv(n, spec=spec, device=0, tune=_tune(grid, 1, envs_per_block), **kw)
     for e in (a, b):
         e.reset(seed=seed)
         assert "k_envq" in e.step_kernel(), e.step_kernel()

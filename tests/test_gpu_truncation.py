@@ -154,6 +154,46 @@ def test_envq_persistent_L2():
     _check_regime(run.flags, L)
 
 
+@pytest.mark.parametrize("name", ["3x3", "9x8"])
+def test_truncation_inside_a_launch_of_several_ticks(name):
+    """pgtg_step_many on a k_envq handle (k_envq<BIG, true>): 12 ticks in launches of 5 and 7 under
+    a limit of 4 steps, 71 blocks of 16 envs on 8 workgroups.  The step count lives in the env record from
+    tick to tick inside a launch, and a truncated env takes its ring head like a terminated one: every env's
+    digest after each call against the restatement's, whose flags show truncations at ticks that are not
+    the last of their launch (the first ones at tick 3)."""
+    from pgtg_amd.digest import Digest
+    from pgtg_amd.vector import PGTGVecEnv
+    conf = CFG2 if name == "3x3" else dict(random_map_width=9, random_map_height=8)
+    spec, n, T, L, calls = _spec(conf), 16 * 70 + 5, 12, 4, ((0, 5), (5, 12))
+    ref, flags = oracle.rollout_digest(spec, n, T, ACT_SEED, max_episode_steps=L, flags_out=True)
+    _check_regime(flags, L)
+    print(name, "truncations", int((flags & 2).astype(bool).sum()), "terminations", int((flags & 1).sum()),
+          "first truncation at tick", int(np.nonzero((flags & 2).any(1))[0][0]))
+    inside = [t for lo, hi in calls for t in range(lo, hi - 1) if (flags[t] & 2).any()]
+    assert 3 in inside and any(t >= 5 for t in inside), inside  # in both launches, not at their last tick
+    assert len(np.unique(ref)) >= 1000, "degenerate digests"
+    env = PGTGVecEnv(n, spec=spec, device=0, autoreset=True, max_episode_steps=L,
+                     tune=dict(queue_mode=1, envs_per_block=16, queue_grid=8))
+    try:
+        env.reset(seed=0)
+        assert env.step_kernel() == (K_ENVQ if name == "3x3" else "pgtg::k_envq<true>"), env.step_kernel()
+        assert env.launch_info()[0] == 16
+        acts = env.random_actions(T, ACT_SEED)
+        dg, l0, e0 = Digest(env), env.step_launches(), env.counters()[1]
+        for lo, hi in calls:
+            env.step_many(acts[lo:hi])
+            got = dg.step_digest().cpu().numpy().view(np.uint64)
+            bad = np.argwhere(got != ref[hi - 1])
+            assert bad.size == 0, f"{name} tick {hi - 1}: {len(bad)} env digests differ, first {bad[:8].ravel().tolist()}"
+            trunc = env.truncated.cpu().numpy()
+            assert np.array_equal(trunc, (flags[hi - 1] & 2) != 0), f"{name} tick {hi - 1}: truncated flags"
+        assert env.step_launches() - l0 == len(calls)  # (several ticks per launch: the path this case is for)
+        assert env.counters()[1] - e0 == int((flags != 0).sum())
+        assert env.error_count()[0] == 0
+    finally:
+        env.close()
+
+
 # ---- the outputs outside the digest, env by env ----------------------------------------------------
 
 DIRECT = {
