@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/pgtg.h"
+#include "pgtg_records.h"
 
 namespace pgtg {
 
@@ -18,12 +19,6 @@ constexpr int kMaxBorder = 192;   // border-connection candidates (<= 2w+2h-2)
 constexpr int kMaxWin = PGTG_MAX_WINDOW;
 constexpr int kBlock = 256;       // lanes (= envs) per workgroup for the step kernels
 constexpr int kSpCache = 24;      // spawner-list entries k_env keeps in LDS (the rest are read from HBM)
-
-// agent flags (EnvRec.w2 bits 16..23)
-constexpr uint32_t kFlagTerminated = 1u << 0;
-constexpr uint32_t kFlagFlatTire = 1u << 1;
-constexpr uint32_t kFlagBraking = 1u << 2;
-constexpr uint32_t kFlagTruncated = 1u << 3;
 
 // per-square feature flags (square_flags)
 constexpr uint32_t SQ_WALL = 1u << 0, SQ_SUBGOAL = 1u << 1, SQ_USED = 1u << 2, SQ_FINAL = 1u << 3,
@@ -38,15 +33,6 @@ __host__ __device__ inline uint32_t plan_exits(uint32_t p) { return p & 15u; }
 __host__ __device__ inline uint32_t plan_otype(uint32_t p) { return (p >> 4) & 7u; }
 __host__ __device__ inline uint32_t plan_omask(uint32_t p) { return (p >> 7) & 15u; }
 __host__ __device__ inline int plan_sgdir(uint32_t p) { return (int)((p >> 11) & 7u) - 1; }
-
-// EnvRec (32 B, one uint4 pair per env):
-//  w0 = px | py<<16 (int16)   w1 = vx | vy<<16 (int16)   w2 = phase | flags<<16 (4 bits) | path_len<<20
-//  w3 = elapsed steps         w4 = start_tile | start_dir<<8 | goal_tile<<16 | goal_dir<<24
-//  w5 = spawn counter (SeedSequence children spawned)   w6,w7 = used-subgoal tile mask (u64; maps of <= 64
-//  tiles, larger maps mark the plan words, kPlanUsed)
-struct EnvRec {
-  uint4 a, b;
-};
 
 struct DevCfg {
   int32_t tw, th, nt, W, H;
@@ -173,12 +159,10 @@ struct DevState {
   uint32_t* visited;      // [n][vis_words] or null
   // traffic: one bank of car slots per env in id order (= the reference's list order), slot-major /
   // env-minor ([slots][n]) so that the lanes of a wave read or write slot k of their envs with one
-  // coalesced access.  w0 = x | y<<8 | route<<16 | profile<<21 | delay<<24 (bit 31: empty slot, a
-  // despawned car), w1 = patience counter, id = car id.  Survivors are rewritten in place, respawns
-  // appended behind the tail, the slots compacted when a tick's respawns could overrun them.
-  // traf[n] = {n_cars | n_spawners<<16, next_id, tail (slots in use), flags}: flags bit 0 = the
-  // occupancy counters are exact for the env's current cars (else k_env rebuilds them from the car
-  // slots), bit 1 = fresh: the env's cars and counters are still in its staging block (below).
+  // coalesced access.  w0 = the car word (pgtg_records.h car_pack), w1 = patience counter, id = car id.
+  // Survivors are rewritten in place, respawns appended behind the tail, the slots compacted when a
+  // tick's respawns could overrun them.
+  // traf[n]: the env's traffic record (pgtg_records.h traf_pack).
   // occ: the 4-bit lane-square occupancy counters (nt * 4 words per env, slot-major [word][n]) as the
   // last launch left them.
   // fresh: per env one contiguous staging block ([n][fresh_dw]) that k_traffic writes for an env it
@@ -189,7 +173,7 @@ struct DevState {
   uint32_t* car_w0;
   uint32_t* car_w1;
   uint32_t* car_id;
-  uint4* traf;
+  Quad* traf;
   uint32_t* occ;          // [nt * 4][n] or null
   uint32_t* fresh;        // [n][fresh_dw] or null
   uint16_t* spawners;     // [n][sp_pitch] square codes x | y<<8, x-major order (env-major: written once
@@ -199,8 +183,7 @@ struct DevState {
   uint32_t* tr_count;     // [2] list lengths, alternating launches
   // map queue (k_envq): per env a ring of kQueueDepth slots, entry = plan words then {px | py<<16, sg,
   // path_len | error<<16, spawn tag}: the live episode's plan (cur) and the next two episodes' maps
-  // (head, spare); qstate = cur slot | head slot << 2 | kQueueStale.  (k_envb: three queued maps,
-  // qstate = held | head << 2.)
+  // (head, spare), or for k_envb three queued maps; qstate: pgtg_records.h queue_state / blockq_state.
   uint32_t* qbuf;         // [n][kQueueDepth][qrec_dw] or null
   uint8_t* qstate;        // [n] or null
   uint2* qreq;            // [2][grid][cap] refill requests {env << 2 | slot, spawn counter} per k_envq

@@ -105,12 +105,16 @@ __device__ __forceinline__ void stage_plan(const uint16_t* __restrict__ plan, in
 // Diagnostic build only (-DPGTG_STAMPS): per-wave phase timestamps (s_memtime) into a debug buffer
 // that nothing else reads.  The product build compiles these to nothing.
 #ifdef PGTG_STAMPS
-__device__ unsigned long long g_stamps[1 << 21];
+constexpr int kStampWords = 2097152;  // 2^21
+__device__ unsigned long long g_stamps[kStampWords];
+// word k (< 32) of the wave's row = value; the caller picks the lane that writes
+#define STAMPV(k, value) \
+  (g_stamps[((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 32 + (k)) & (kStampWords - 1)] = (value))
 #define STAMP(k)                                                                          \
   do {                                                                                    \
     if ((threadIdx.x & 63) == 0) {                                                        \
       unsigned long long t_ = __builtin_amdgcn_s_memtime();                               \
-      g_stamps[((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 32 + (k)) & ((1 << 21) - 1)] = t_; \
+      STAMPV(k, t_);                                                                      \
     }                                                                                     \
   } while (0)
 // wall-clock (s_memrealtime, 100 MHz, one clock for the chip) stamp k in {0, 1} of the wave
@@ -154,41 +158,9 @@ __device__ __forceinline__ int seg_dir(int lx, int ly) {
   return -1;
 }
 
-struct EnvView {
-  int px, py, vx, vy;
-  uint32_t phase, flags, path_len, elapsed;
-  uint32_t sg, spawn;
-  uint64_t used;
-};
-
-__device__ __forceinline__ EnvView rec_view(const EnvRec& e) {
-  EnvView v;
-  v.px = (int)(int16_t)(e.a.x & 0xffffu);
-  v.py = (int)(int16_t)(e.a.x >> 16);
-  v.vx = (int)(int16_t)(e.a.y & 0xffffu);
-  v.vy = (int)(int16_t)(e.a.y >> 16);
-  v.phase = e.a.z & 0xffffu;
-  v.flags = (e.a.z >> 16) & 0xfu;
-  v.path_len = e.a.z >> 20;
-  v.elapsed = e.a.w;
-  v.sg = e.b.x;
-  v.spawn = e.b.y;
-  v.used = (uint64_t)e.b.z | ((uint64_t)e.b.w << 32);
-  return v;
-}
+// an env's record as fields and back (pgtg_records.h holds the layout)
 __device__ __forceinline__ EnvView rec_load(const EnvRec* r, uint64_t i) { return rec_view(r[i]); }
-__device__ __forceinline__ void rec_store(EnvRec* r, uint64_t i, const EnvView& v) {
-  EnvRec e;
-  e.a.x = ((uint32_t)v.px & 0xffffu) | ((uint32_t)v.py << 16);
-  e.a.y = ((uint32_t)v.vx & 0xffffu) | ((uint32_t)v.vy << 16);
-  e.a.z = (v.phase & 0xffffu) | ((v.flags & 0xfu) << 16) | (v.path_len << 20);
-  e.a.w = v.elapsed;
-  e.b.x = v.sg;
-  e.b.y = v.spawn;
-  e.b.z = (uint32_t)v.used;
-  e.b.w = (uint32_t)(v.used >> 32);
-  r[i] = e;
-}
+__device__ __forceinline__ void rec_store(EnvRec* r, uint64_t i, const EnvView& v) { r[i] = rec_pack(v); }
 
 // Tiles >= nt of a plan word (two u16 tiles per word) are padding, stored as 0 so that the device
 // state is a function of the seeds alone (LDS plan rows may hold stale bytes there).
@@ -197,13 +169,6 @@ __device__ __forceinline__ uint32_t plan_word_mask(const DevCfg& c, int word) {
   return t0 + 1 < c.nt ? ~0u : (t0 < c.nt ? 0xffffu : 0u);
 }
 constexpr int kQueueDepth = 3;   // ring slots per env of k_envq: the live episode's map (cur) and the next two's
-// qstate of a k_envq handle: cur slot | head slot << 2 (| kQueueStale); the third slot is the spare
-// (two bits as a slot index: never outside the ring, whatever the byte holds)
-__host__ __device__ inline uint32_t queue_slot(uint32_t bits) { return (bits & 3u) < 2u ? (bits & 3u) : 2u; }
-__host__ __device__ inline uint32_t queue_cur(uint32_t qs) { return queue_slot(qs); }
-__host__ __device__ inline uint32_t queue_head(uint32_t qs) { return queue_slot(qs >> 2); }
-// the spare of a ring whose cur and head differ (else cur's successor's successor: still a slot)
-__host__ __device__ inline uint32_t queue_spare(uint32_t qc, uint32_t qh) { return qc != qh ? 3u - qc - qh : (qc + 2u) % 3u; }
 // Where env i's live tile plan is: its row of S.plan, or, in a k_envq handle (which has no S.plan), the
 // ring slot that holds its episode (cur).  Every reader and writer of an env's plan goes through here.
 // SLOT is a compile-time choice in the step kernels (k_env has an instance of its own for k_envq handles,
@@ -268,8 +233,8 @@ __device__ __forceinline__ uint32_t square_flags(const DevCfg& c, const Plan& pl
   int d = seg_dir(lx, ly);
   if (d >= 0 && ((ex >> d) & 1u)) {
     if (plan_sgdir(p) == d) f |= used_bit<BIG>(v, p, t) ? SQ_USED : SQ_SUBGOAL;
-    if ((int)(v.sg & 0xffu) == t && (int)((v.sg >> 8) & 0xffu) == d) f |= SQ_START;
-    if ((int)((v.sg >> 16) & 0xffu) == t && (int)(v.sg >> 24) == d) f |= SQ_FINAL;
+    if (sg_start_tile(v.sg) == t && sg_start_dir(v.sg) == d) f |= SQ_START;
+    if (sg_goal_tile(v.sg) == t && sg_goal_dir(v.sg) == d) f |= SQ_FINAL;
   }
   // (read unconditionally, at a valid row: a conditional LDS read is a branch waited on alone)
   const uint32_t ob = bit81(sT.obst[min(plan_omask(p), (uint32_t)PGTG_N_OBST_MASKS - 1u)], sq);
@@ -393,7 +358,6 @@ __device__ __forceinline__ int profile_of(const ProfileCdf& p, uint64_t u) {
   return prof;
 }
 
-constexpr uint32_t kCarEmpty = 1u << 31;  // w0 of a slot without a car
 // One env's car slots (DevState::car_w0 layout: slot k of env i at k * n + i) through per-lane
 // pointers at the env's slot 0: the three array bases stay in VGPRs instead of being re-read from
 // spilled scalar registers at every access of the car loops.
@@ -415,7 +379,6 @@ struct CarSlots {
 __device__ __forceinline__ gu32* fresh_block(const DevState& S, uint64_t i) {
   return (gu32*)(S.fresh + i * (uint64_t)S.fresh_dw);
 }
-constexpr uint32_t kTrafOccValid = 1u, kTrafFresh = 2u;  // traf.w flags
 
 // ------------------------------------------------------------------------------------------------
 // reset: seeding, procedural map, compilation, start square  (pgtg/environment.py:581-656)
@@ -717,8 +680,8 @@ __device__ __forceinline__ void remove_edges(const DevCfg& c, const uint32_t* __
   }
 #ifdef PGTG_STAMPS
   if ((threadIdx.x & 63) == 0) {  // lane 0's loop: cycles in the connectivity test, iterations
-    g_stamps[((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 32 + 26) & ((1 << 21) - 1)] = dbg_bfs;
-    g_stamps[((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 32 + 27) & ((1 << 21) - 1)] = dbg_iters;
+    STAMPV(26, dbg_bfs);
+    STAMPV(27, dbg_iters);
   }
 #endif
 }
@@ -1096,11 +1059,6 @@ __device__ __forceinline__ int compile_generated(const DevCfg& c, uint16_t* plan
   return c.nt <= 32 ? compile_path<uint32_t>(c, plan, s, g) : compile_path<uint64_t>(c, plan, s, g);
 }
 
-struct TrafState {
-  uint32_t n_cars, n_spawners, next_id, tail;  // tail: car slots in use (cars and empty slots)
-  uint32_t fresh;  // the cars are still in the env's staging block (traf.w kTrafFresh)
-};
-
 // spawner squares of local column lx of tile (tx, ty): lane-data spawners (dead ends) plus the
 // border rule of pgtg/parser.py:120-148 ("car_lane all right" on the west border, ...)
 __device__ __forceinline__ uint32_t spawner_colmask(const DevCfg& c, uint32_t ex, int tx, int ty, int lx) {
@@ -1165,7 +1123,7 @@ __device__ __forceinline__ void car_squares(const DevCfg& c, const Plan& pl, con
 // A fresh car m of the env: w0 into the env's staging block (patience 0 and id m are implied by the
 // fresh flag).  The lanes of a group write runs of consecutive words.
 __device__ __forceinline__ void store_new_car(gu32* fw, const CarSquare& q, int route, int prof, int m) {
-  fw[m] = (uint32_t)q.x | (uint32_t)q.y << 8 | (uint32_t)route << 16 | (uint32_t)prof << 21;
+  fw[m] = car_pack(q.x, q.y, route, prof, 0);
 }
 
 // The per-car draws on one lane, in id order: random() -> profile, then choice(routes) when the
@@ -1640,10 +1598,10 @@ __device__ __forceinline__ int env_reset(const DevCfg& c, const DevState& S, uin
   int len;
   if (c.fixed_map) {
     for (int t = 0; t < c.nt; t++) plan[t] = c.fixed_plan[t];
-    st_t = (int)(c.fixed_sg & 0xffu);
-    st_d = (int)((c.fixed_sg >> 8) & 0xffu);
-    gl_t = (int)((c.fixed_sg >> 16) & 0xffu);
-    gl_d = (int)(c.fixed_sg >> 24);
+    st_t = sg_start_tile(c.fixed_sg);
+    st_d = sg_start_dir(c.fixed_sg);
+    gl_t = sg_goal_tile(c.fixed_sg);
+    gl_d = sg_goal_dir(c.fixed_sg);
     STAMP(10);
     len = BIG ? compile_path<Bits<4>>(c, plan, st_t, gl_t)
               : (c.nt <= 32 ? compile_path<uint32_t>(c, plan, st_t, gl_t) : compile_path<uint64_t>(c, plan, st_t, gl_t));
@@ -1653,7 +1611,7 @@ __device__ __forceinline__ int env_reset(const DevCfg& c, const DevState& S, uin
     STAMP(10);
     len = compile_generated<BIG>(c, plan, st_t, gl_t, ix);
   }
-  v.sg = (uint32_t)st_t | (uint32_t)st_d << 8 | (uint32_t)gl_t << 16 | (uint32_t)gl_d << 24;
+  v.sg = sg_word(st_t, st_d, gl_t, gl_d);
   STAMP(11);
   v.used = 0;
   v.path_len = (uint32_t)max(len, 0);
@@ -1720,7 +1678,7 @@ template <bool BIG>
 __device__ __forceinline__ bool nearest_goal_square(const DevCfg& c, const Plan& pl, const EnvView& v, int x, int y, int& bx, int& by) {
   int best = 0x7fffffff;
   bool found = false;
-  int gl_t = (int)((v.sg >> 16) & 0xffu), gl_d = (int)(v.sg >> 24);
+  int gl_t = sg_goal_tile(v.sg), gl_d = sg_goal_dir(v.sg);
   for (int t = 0; t < c.nt; t++) {
     uint32_t p = pl[t];
     int d = -1;
@@ -1814,8 +1772,8 @@ __device__ __forceinline__ void tile_chan(const DevCfg& c, const EnvView& v, uin
   const uint32_t ex = plan_exits(p), ot = plan_otype(p);
   const int sd = plan_sgdir(p);
   const bool used = used_bit<BIG>(v, p, t);
-  const int st_t = (int)(v.sg & 0xffu), st_d = (int)((v.sg >> 8) & 0xffu);
-  const int gl_t = (int)((v.sg >> 16) & 0xffu), gl_d = (int)(v.sg >> 24);
+  const int st_t = sg_start_tile(v.sg), st_d = sg_start_dir(v.sg);
+  const int gl_t = sg_goal_tile(v.sg), gl_d = sg_goal_dir(v.sg);
   const bool sg_on = sd >= 0 && ((ex >> sd) & 1u), fi_on = t == gl_t && ((ex >> gl_d) & 1u);
   const bool st_on = t == st_t && ((ex >> st_d) & 1u);
   const uint32_t om = min(plan_omask(p), (uint32_t)PGTG_N_OBST_MASKS - 1u);
@@ -1906,8 +1864,8 @@ __device__ __forceinline__ void build_obs(const DevCfg& c, const DevState& S, co
     uint32_t W3[3], SG[3] = {0, 0, 0}, US[3] = {0, 0, 0}, FI[3] = {0, 0, 0}, ST[3] = {0, 0, 0}, OB[3] = {0, 0, 0};
     int sd = plan_sgdir(p);
     bool used = used_bit<BIG>(v, p, t);
-    int st_t = (int)(v.sg & 0xffu), st_d = (int)((v.sg >> 8) & 0xffu);
-    int gl_t = (int)((v.sg >> 16) & 0xffu), gl_d = (int)(v.sg >> 24);
+    int st_t = sg_start_tile(v.sg), st_d = sg_start_dir(v.sg);
+    int gl_t = sg_goal_tile(v.sg), gl_d = sg_goal_dir(v.sg);
     uint32_t ot = plan_otype(p);
     uint32_t CR[3] = {0, 0, 0};  // squares of this tile holding a car
     if ((TR && c.need_car) && occ && ex) {
@@ -2153,8 +2111,8 @@ __device__ __forceinline__ void build_obs(const DevCfg& c, const DevState& S, co
   if (c.next_subgoal && head) {
     int t = ty * c.tw + tx;
     int sd = plan_sgdir(pl[t]);
-    int gl_t = (int)((v.sg >> 16) & 0xffu);
-    int nsd = sd >= 0 ? sd : (t == gl_t ? (int)(v.sg >> 24) : -1);
+    int gl_t = sg_goal_tile(v.sg);
+    int nsd = sd >= 0 ? sd : (t == gl_t ? sg_goal_dir(v.sg) : -1);
     if (nsd == -1 || c.sliding) {
       int bx = 0, by = 0;
       if (nearest_goal_square<BIG>(c, pl, v, pix, piy, bx, by))
@@ -2199,8 +2157,8 @@ __device__ __noinline__ int recount_slot(const DevCfg& c, const Plan& pl, const 
   for (int k = 0; k < t_out; k++) {
     if (k >= w && k <= r) continue;
     const uint32_t w0 = (fw0 && k > r && k < tail0) ? fw0[k] : cs.w0[cs.at(k)];
-    if (w0 & kCarEmpty) continue;
-    n += lane_slot(c, pl, (int)(w0 & 255u), (int)((w0 >> 8) & 255u)) == s ? 1 : 0;
+    if (car_empty(w0)) continue;
+    n += lane_slot(c, pl, car_x(w0), car_y(w0)) == s ? 1 : 0;
   }
   return n;
 }
@@ -2262,9 +2220,9 @@ __device__ __forceinline__ int move_cars(const DevCfg& c, const DevState& S, uin
     npat = fresh ? 0u : npat;
     if (pack) nid = cs.id[ar];
     nid = fresh ? rn : nid;
-    if (!(a & kCarEmpty)) {
-      const int x = (int)(a & 255u), y = (int)((a >> 8) & 255u), prof = (int)((a >> 21) & 7u);
-      int route = (int)((a >> 16) & 31u), delay = (int)((a >> 24) & 3u);
+    if (!car_empty(a)) {
+      const int x = car_x(a), y = car_y(a), prof = car_profile(a);
+      int route = car_route(a), delay = car_delay(a);
       // ---- map lookups (no draws).  Every LDS read is unconditional at a valid index (a conditional
       // read is a branch the compiler cannot hoist the read out of, and each one waited alone); the
       // reads of one level go out together.
@@ -2366,7 +2324,7 @@ __device__ __forceinline__ int move_cars(const DevCfg& c, const DevState& S, uin
         const uint32_t r5 = nr > 1u ? (uint32_t)pcg_draw(ca, true, nr) : 0u;
         const int nroute = sTX.lane_route[kth_bit(rl, (int)r5)];
         if (!pack) cs.w0[aw] = kCarEmpty;
-        cs.w0[an] = (uint32_t)sx | (uint32_t)sy << 8 | (uint32_t)nroute << 16 | (uint32_t)nprof << 21;
+        cs.w0[an] = car_pack(sx, sy, nroute, nprof, 0);
         cs.w1[an] = 0u;
         cs.id[an] = ts.next_id++;
         an += nst;
@@ -2395,7 +2353,7 @@ __device__ __forceinline__ int move_cars(const DevCfg& c, const DevState& S, uin
           hist[route]++;
         }
         const uint64_t ao = pack ? ap : aw;
-        cs.w0[ao] = (uint32_t)nx | (uint32_t)ny << 8 | (uint32_t)route << 16 | (uint32_t)prof << 21 | (uint32_t)delay << 24;
+        cs.w0[ao] = car_pack(nx, ny, route, prof, delay);
         cs.w1[ao] = pat;
         if (pack) {
           cs.id[ao] = id;
@@ -2521,7 +2479,7 @@ __device__ __forceinline__ int env_step(const DevCfg& c, const DevState& S, uint
   double m = 0.0;
   if (dx != 0 && dy != 0) m = xmajor ? (double)dy / (double)adx : (double)dx / (double)ady;
   int prev_minor = 0;
-  const int gl_t = (int)((v.sg >> 16) & 0xffu), gl_d = (int)(v.sg >> 24);
+  const int gl_t = sg_goal_tile(v.sg), gl_d = sg_goal_dir(v.sg);
   const int color = phase_color(c, v.phase);
   // the subgoal reward of this episode's path (one read for every subgoal the step may cross)
   const double ind_pl = BIG ? c.ind_reward[v.path_len] : sT.ind[v.path_len];
@@ -2863,7 +2821,6 @@ __host__ __device__ inline uint64_t queue_req_cap(uint64_t nblk, uint64_t grid, 
 }
 constexpr uint64_t kStaggerMaxTicks = 20000;  // 200 us of 100 MHz wall clock: a bound, never reached
 constexpr int kBlockDepth = 3;   // of k_envb (the rings refilled per block)
-constexpr uint32_t kQueueStale = 0x80u;  // qstate flag: the ring's entries are not this env's (k_qfill)
 constexpr int kViewDw = 8;       // k_envq with <= 32 envs: an env's view words for the image builders
 // k_envq's line masks of the changed observations (lm_words words each), in LDS it leaves unused: the reset
 // hand-over words (scratch_dw per env, k_env's).  Two, one per block parity: its waves read a block's mask in
@@ -3068,13 +3025,7 @@ __global__ void __launch_bounds__(kBlock, TR ? 3 : 4) k_env(const DevCfg* __rest
     v = rec_load(S.rec, i);
     if (mode == MODE_STEP) act = actions[i];  // issued with the staging loads, not on the step's chain
     if ((TR && c.need_car)) {
-      uint4 tr4 = S.traf[i];
-      ts.n_cars = tr4.x & 0xffffu;
-      ts.n_spawners = tr4.x >> 16;
-      ts.next_id = tr4.y;
-      ts.tail = tr4.z;
-      ts.fresh = (tr4.w & kTrafFresh) ? 1u : 0u;
-      occ_valid = (tr4.w & kTrafOccValid) != 0u;
+      traf_unpack(S.traf[i], ts, occ_valid);
     }
     stage_plan<BIG>(plan_row<SLOT>(c, S, i), c.plan_dq, plan_w, L.plan_stride_dw);
   }
@@ -3117,10 +3068,10 @@ __global__ void __launch_bounds__(kBlock, TR ? 3 : 4) k_env(const DevCfg* __rest
       // slots past the tail as slot 0), their reads batched; then the counter updates in order
       int sl[16];
 #pragma unroll
-      for (int g = 0; g < 16; g++) sl[g] = lane_slot_tw(tw, pl, (int)(a16[g] & 255u), (int)((a16[g] >> 8) & 255u));
+      for (int g = 0; g < 16; g++) sl[g] = lane_slot_tw(tw, pl, car_x(a16[g]), car_y(a16[g]));
 #pragma unroll
       for (int g = 0; g < 16; g++) {
-        if (k0 + g < tail && !(a16[g] & kCarEmpty)) {
+        if (k0 + g < tail && !car_empty(a16[g])) {
           if (sl[g] < 0) err = PGTG_E_UNSUPPORTED;
           else occ_inc(occ, sl[g], occ_sat);
         }
@@ -3288,8 +3239,7 @@ __global__ void __launch_bounds__(kBlock, TR ? 3 : 4) k_env(const DevCfg* __rest
       rec_store(S.rec, i, v);
       // (a reset env's counters come from k_traffic with its fresh cars; until then invalid)
       if ((TR && c.need_car))
-        S.traf[i] = make_uint4(ts.n_cars | ts.n_spawners << 16, ts.next_id, ts.tail,
-                               (occ_valid && !reset_now ? kTrafOccValid : 0u) | (ts.fresh ? kTrafFresh : 0u));
+        S.traf[i] = traf_pack(ts, (occ_valid && !reset_now ? kTrafOccValid : 0u) | (ts.fresh ? kTrafFresh : 0u));
     }
     if (mode != MODE_OBSERVE || err) S.err[i] = (uint8_t)(-err);
     // maps generated here: the queued ones are stale (a k_envq handle's cur slot, which holds the new plan, stays)
@@ -3334,10 +3284,6 @@ __global__ void __launch_bounds__(kBlock, TR ? 3 : 4) k_env(const DevCfg* __rest
 // start square -- depends only on (seed, spawn counter), not on the episode before it, so the next
 // two episodes' maps of every env are generated ahead and a reset takes the head of the env's ring.
 // ------------------------------------------------------------------------------------------------
-// EnvView::sg, the start/goal word of a map: start tile, start direction, goal tile, goal direction
-__device__ __forceinline__ uint32_t sg_word(int st_t, int st_d, int gl_t, int gl_d) {
-  return (uint32_t)st_t | (uint32_t)st_d << 8 | (uint32_t)gl_t << 16 | (uint32_t)gl_d << 24;
-}
 // A generated map's meta quad, packed and read in one place for k_envb and the fill kernels: start square px | py << 16, start/goal word,
 // path length | -error << 16, and the tag of the spawn counter the map was made for.  It is the 16 bytes
 // behind the tile plan of a map-ring entry: gen_queue_entry packs it, ring_take returns it to k_envb.
@@ -3892,7 +3838,7 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
         else
           req_new[p] = r;
         // the roles rotate: head -> cur, spare -> head  (every env's byte instead: 403.3 vs 401.4 us)
-        S.qstate[i] = (uint8_t)(qh | queue_spare(qc, qh) << 2);
+        S.qstate[i] = queue_state(qh, queue_spare(qc, qh));
       }
     }
     // FUSED, a workgroup that owns one block: its byte for the next tick, read back behind this tick's store
@@ -4011,7 +3957,7 @@ __global__ void __launch_bounds__(kBlock, 4) k_envb(const DevCfg* __restrict__ c
     xf[slot * L.scratch_dw] = v.spawn;
     xf[slot * L.scratch_dw + 1] = qs;
   }
-  const uint32_t qn = qs & 3u, qh = (qs >> 2) & 3u;
+  const uint32_t qn = blockq_held(qs), qh = blockq_head(qs);
   if (env_wave) {  // refills: ring level l (0 = head) for the envs holding <= l maps
 #pragma unroll
     for (int l = 0; l < kBlockDepth; l++) {
@@ -4034,8 +3980,7 @@ __global__ void __launch_bounds__(kBlock, 4) k_envb(const DevCfg* __restrict__ c
   const bool any_empty = F[0] != 0;
 #ifdef PGTG_STAMPS
   if ((threadIdx.x & 63) == 0)  // diagnostic: empty rings and level-1/2 refills wanted in this workgroup
-    g_stamps[((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 32 + 12) & ((1 << 21) - 1)] =
-        (unsigned long long)F[0] | (unsigned long long)F[1] << 16 | (unsigned long long)F[2] << 32;
+    STAMPV(12, (unsigned long long)F[0] | (unsigned long long)F[1] << 16 | (unsigned long long)F[2] << 32);
 #endif
 
   if (wave == gen_wave) {
@@ -4050,7 +3995,7 @@ __global__ void __launch_bounds__(kBlock, 4) k_envb(const DevCfg* __restrict__ c
       }
       const uint64_t ie = env0 + e;
       const uint32_t qe = xf[e * L.scratch_dw + 1];
-      const uint32_t rslot = (((qe >> 2) & 3u) + (uint32_t)l) % (uint32_t)kBlockDepth;
+      const uint32_t rslot = (blockq_head(qe) + (uint32_t)l) % (uint32_t)kBlockDepth;
       gen_queue_entry<BIG>(c, S, ie, xf[e * L.scratch_dw] + 5u * (uint32_t)l, gplan, pdw,
                       S.qbuf + (ie * kBlockDepth + rslot) * (uint64_t)c.qrec_dw, ABLATE(L, 16), !ABLATE(L, 512));
     };
@@ -4156,7 +4101,7 @@ __global__ void __launch_bounds__(kBlock, 4) k_envb(const DevCfg* __restrict__ c
     }
     const uint32_t nq = reset_now ? have - 1u : have;  // have >= 1: every head is refilled
     const uint32_t nh = reset_now ? (qh + 1u) % (uint32_t)kBlockDepth : qh;
-    S.qstate[i] = (uint8_t)(nq | nh << 2);
+    S.qstate[i] = blockq_state(nq, nh);
   }
   STAMP(5);
   {
@@ -4203,10 +4148,10 @@ __global__ void __launch_bounds__(kBlock) k_qfill(const DevCfg* __restrict__ cfg
     // the cur slot holds the live plan (a reset launch's k_env wrote it there) and keeps its place; a
     // stale ring's head and spare are the two slots after it
     const uint32_t qc = queue_cur(qs);
-    const bool stale = (qs & kQueueStale) != 0 || queue_head(qs) == qc || ((qs >> 2) & 3u) == 3u;
+    const bool stale = (qs & kQueueStale) != 0 || queue_head(qs) == qc || queue_head_bad(qs);
     const uint32_t qh = stale ? (qc + 1u) % 3u : queue_head(qs);
     const uint32_t qsp = queue_spare(qc, qh);
-    const uint32_t spawn = S.rec[i].b.y;  // EnvRec w5
+    const uint32_t spawn = rec_spawn(S.rec[i]);
     const int tag_w = c.plan_dq * 4 + 3;
     uint16_t* plan = reinterpret_cast<uint16_t*>(lds + threadIdx.x * pdw);
     for (uint32_t l = 0; l < 2u; l++) {
@@ -4216,7 +4161,7 @@ __global__ void __launch_bounds__(kBlock) k_qfill(const DevCfg* __restrict__ cfg
         made++;
       }
     }
-    if (stale) S.qstate[i] = (uint8_t)(qc | qh << 2);
+    if (stale) S.qstate[i] = queue_state(qc, qh);
   }
   count_maps(S, made);
 }
@@ -4234,14 +4179,14 @@ __global__ void __launch_bounds__(kBlock) k_qfill_b(const DevCfg* __restrict__ c
   uint32_t made = 0;
   if (i < S.n) {
     const uint32_t qs = S.qstate[i];
-    const uint32_t qn = (qs & kQueueStale) ? 0u : (qs & 3u), qh = (qs & kQueueStale) ? 0u : ((qs >> 2) & 3u);
+    const uint32_t qn = (qs & kQueueStale) ? 0u : blockq_held(qs), qh = (qs & kQueueStale) ? 0u : blockq_head(qs);
     if (qn < (uint32_t)kBlockDepth) {
-      const uint32_t spawn = S.rec[i].b.y;  // EnvRec w5
+      const uint32_t spawn = rec_spawn(S.rec[i]);
       uint16_t* plan = reinterpret_cast<uint16_t*>(lds + threadIdx.x * pdw);
       for (uint32_t l = qn; l < (uint32_t)kBlockDepth; l++)
         gen_queue_entry<BIG>(c, S, i, spawn + 5u * l, plan, pdw,
                              S.qbuf + (i * kBlockDepth + (qh + l) % (uint32_t)kBlockDepth) * (uint64_t)c.qrec_dw);
-      S.qstate[i] = (uint8_t)((uint32_t)kBlockDepth | qh << 2);
+      S.qstate[i] = blockq_state((uint32_t)kBlockDepth, qh);
       made = (uint32_t)kBlockDepth - qn;
     }
   }
@@ -4279,10 +4224,9 @@ __global__ void __launch_bounds__(kBlock) k_gen_bench(const DevCfg* __restrict__
       chk += (uint32_t)len + plan[st_t];
     }
   }
-  const uint64_t wv = (uint64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
   if ((threadIdx.x & 63) == 0) {
-    g_stamps[(wv * 32 + 0) & ((1 << 21) - 1)] = tg;
-    g_stamps[(wv * 32 + 1) & ((1 << 21) - 1)] = tc;
+    STAMPV(0, tg);
+    STAMPV(1, tc);
   }
   if (chk == 0xdeadbeefu) S.err[i] = 1;  // keeps the work alive
 }
@@ -4318,8 +4262,8 @@ __global__ void __launch_bounds__(kBlock) k_traffic(const DevCfg* __restrict__ c
   STAMP(25);
 #ifdef PGTG_STAMPS
   if ((threadIdx.x & 63) == 0)  // the launch's shape (last launch): list length, rounds, envs per wave, capacity
-    g_stamps[((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 32 + 15) & ((1 << 21) - 1)] =
-        (unsigned long long)n | (unsigned long long)rounds << 32 | (unsigned long long)e << 40 | (unsigned long long)cap_w << 48;
+    STAMPV(15, (unsigned long long)n | (unsigned long long)rounds << 32 | (unsigned long long)e << 40 |
+                   (unsigned long long)cap_w << 48);
 #endif
   if ((uint32_t)slot >= e) return;
   const int ls = wave * cap_w + slot;  // LDS slot of the env
@@ -4361,7 +4305,7 @@ __global__ void __launch_bounds__(kBlock) k_traffic(const DevCfg* __restrict__ c
     }
     if (sub == 0) {
       stream_store_state(S.car, i, cr);
-      S.traf[i] = make_uint4(ts.n_cars | ts.n_spawners << 16, ts.next_id, ts.tail, err == 0 ? kTrafOccValid | kTrafFresh : 0u);
+      S.traf[i] = traf_pack(ts, err == 0 ? kTrafOccValid | kTrafFresh : 0u);
       if (err) S.err[i] = (uint8_t)(-err);
       if (c.obs_fast && c.traffic_ch >= 0 && out.obs) {
         // the tile window's traffic channel: k_env wrote it with no cars; set the car squares
@@ -4466,18 +4410,18 @@ __global__ void __launch_bounds__(256) k_car_digest(DevState S, uint64_t* __rest
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= S.n) return;
   constexpr uint64_t CB = 1ull << 40;
-  const uint4 t = S.traf[i];
+  const TrafState t = traf_unpack(S.traf[i]);
   const CarSlots cs(S, i);
-  const bool fresh = (t.w & kTrafFresh) != 0u;
+  const bool fresh = t.fresh != 0u;
   const gu32* fb = fresh_block(S, i);
-  uint64_t d = (uint64_t)(t.x & 0xffffu) * dg_w(CB), j = 0;
-  for (int k = 0; k < (int)t.z; k++) {
+  uint64_t d = (uint64_t)t.n_cars * dg_w(CB), j = 0;
+  for (int k = 0; k < (int)t.tail; k++) {
     const uint32_t w0 = fresh ? fb[k] : cs.w0[cs.at(k)];
-    if (w0 & kCarEmpty) continue;
+    if (car_empty(w0)) continue;
     const uint32_t id = fresh ? (uint32_t)k : cs.id[cs.at(k)];
-    const uint64_t pk = (uint64_t)id | (uint64_t)(w0 & 255u) << 32 | (uint64_t)((w0 >> 8) & 255u) << 40 |
-                        (uint64_t)((w0 >> 16) & 31u) << 48 | (uint64_t)((w0 >> 21) & 7u) << 53 |
-                        (uint64_t)((w0 >> 24) & 3u) << 56;
+    const uint64_t pk = (uint64_t)id | (uint64_t)car_x(w0) << 32 | (uint64_t)car_y(w0) << 40 |
+                        (uint64_t)car_route(w0) << 48 | (uint64_t)car_profile(w0) << 53 |
+                        (uint64_t)car_delay(w0) << 56;
     const uint32_t w1 = fresh ? 0u : cs.w1[cs.at(k)];
     d += (pk + 1) * dg_w(CB + 1 + 2 * j) + (uint64_t)w1 * dg_w(CB + 2 + 2 * j);
     j++;
@@ -4985,7 +4929,7 @@ static int derive_cfg(pgtg_handle* h, const PgtgConfig& in, DevCfg& c) {
     if (in.fm_start[0] < 0 || in.fm_start[0] >= tw || in.fm_start[1] < 0 || in.fm_start[1] >= th || in.fm_goal[0] < 0 ||
         in.fm_goal[0] >= tw || in.fm_goal[1] < 0 || in.fm_goal[1] >= th)
       return fail(h, PGTG_E_INVALID, "fixed map start/goal outside the map");
-    c.fixed_sg = (uint32_t)st | (uint32_t)in.fm_start[2] << 8 | (uint32_t)gl << 16 | (uint32_t)in.fm_goal[2] << 24;
+    c.fixed_sg = sg_word(st, in.fm_start[2], gl, in.fm_goal[2]);
   }
   c.start_mode = in.start_mode;
   c.goal_mode = in.goal_mode;
@@ -5521,7 +5465,8 @@ static int create(pgtg_handle* h, const PgtgConfig* cfg) {
   if (h->L.queue) {
     if (int rc = dalloc(h, &S.qbuf, n * (uint64_t)queue_depth(h) * (uint64_t)c.qrec_dw)) return rc;
     if (int rc = dalloc(h, &S.qstate, n)) return rc;
-    if (h->slot_plan && hipMemset(S.qstate, 0x04, n) != hipSuccess) return fail(h, PGTG_E_DEVICE, "hipMemset failed");
+    if (h->slot_plan && hipMemset(S.qstate, queue_state(0, 1), n) != hipSuccess)
+      return fail(h, PGTG_E_DEVICE, "hipMemset failed");
   }
   if (h->L.queue && !h->q_block) {  // k_envq's request lists, overflow lists and counters
     const uint64_t blocks = (n + h->L.envs - 1) / h->L.envs;
@@ -5822,8 +5767,22 @@ int pgtg_random_actions(pgtg_handle* h, uint8_t* actions_dev, uint64_t seed, uin
   return PGTG_OK;
 }
 
-static int read_traf(pgtg_handle* h, uint64_t env, uint4* t) {
-  HIPCHK(h, hipMemcpy(t, h->S.traf + env, sizeof *t, hipMemcpyDeviceToHost));
+static int read_traf(pgtg_handle* h, uint64_t env, TrafState* t) {
+  Quad q;
+  HIPCHK(h, hipMemcpy(&q, h->S.traf + env, sizeof q, hipMemcpyDeviceToHost));
+  *t = traf_unpack(q);
+  return 0;
+}
+// One env's agent record as fields, and back.
+static int read_rec(pgtg_handle* h, uint64_t env, EnvView* v) {
+  EnvRec r;
+  HIPCHK(h, hipMemcpy(&r, h->S.rec + env, sizeof r, hipMemcpyDeviceToHost));
+  *v = rec_view(r);
+  return 0;
+}
+static int write_rec(pgtg_handle* h, uint64_t env, const EnvView& v) {
+  const EnvRec r = rec_pack(v);
+  HIPCHK(h, hipMemcpy(h->S.rec + env, &r, sizeof r, hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -5846,25 +5805,24 @@ static int read_plan_row(pgtg_handle* h, uint64_t env, std::vector<uint16_t>& p)
 int pgtg_get_env_state(pgtg_handle* h, uint64_t env, PgtgEnvState* st) {
   if (!h || !st || env >= h->n) return PGTG_E_INVALID;
   if (int rc = host_sync(h)) return rc;
-  EnvRec r;
+  EnvView v;
   uint64_t seed;
   uint8_t e;
-  HIPCHK(h, hipMemcpy(&r, h->S.rec + env, sizeof r, hipMemcpyDeviceToHost));
+  if (int rc = read_rec(h, env, &v)) return rc;
   HIPCHK(h, hipMemcpy(&seed, h->S.seed + env, sizeof seed, hipMemcpyDeviceToHost));
   HIPCHK(h, hipMemcpy(&e, h->S.err + env, 1, hipMemcpyDeviceToHost));
   memset(st, 0, sizeof *st);
-  st->x = (int16_t)(r.a.x & 0xffffu);
-  st->y = (int16_t)(r.a.x >> 16);
-  st->vx = (int16_t)(r.a.y & 0xffffu);
-  st->vy = (int16_t)(r.a.y >> 16);
-  st->phase = (int)(r.a.z & 0xffffu);
-  uint32_t fl = (r.a.z >> 16) & 0xfu;
-  st->terminated = (fl & kFlagTerminated) ? 1 : 0;
-  st->flat_tire = (fl & kFlagFlatTire) ? 1 : 0;
-  st->path_len = (int)(r.a.z >> 20);
-  st->elapsed = (int)r.a.w;
-  st->spawn_counter = r.b.y;
-  st->used_subgoals[0] = (uint64_t)r.b.z | ((uint64_t)r.b.w << 32);
+  st->x = v.px;
+  st->y = v.py;
+  st->vx = v.vx;
+  st->vy = v.vy;
+  st->phase = (int)v.phase;
+  st->terminated = (v.flags & kFlagTerminated) ? 1 : 0;
+  st->flat_tire = (v.flags & kFlagFlatTire) ? 1 : 0;
+  st->path_len = (int)v.path_len;
+  st->elapsed = (int)v.elapsed;
+  st->spawn_counter = v.spawn;
+  st->used_subgoals[0] = v.used;
   if (h->hcfg.nt > kSmallTiles) {  // maps of > 64 tiles mark the plan words (kPlanUsed)
     std::vector<uint16_t> p;
     if (int rc = read_plan_row(h, env, p)) return rc;
@@ -5874,25 +5832,25 @@ int pgtg_get_env_state(pgtg_handle* h, uint64_t env, PgtgEnvState* st) {
   st->seed = seed;
   st->error = -(int)e;
   if (h->hcfg.need_car) {
-    uint4 t;
+    TrafState t;
     if (int rc = read_traf(h, env, &t)) return rc;
-    st->n_cars = (int)(t.x & 0xffffu);
-    st->n_spawners = (int)(t.x >> 16);
-    st->next_car_id = (int)t.y;
-    st->car_tail = (int)t.z;
+    st->n_cars = (int)t.n_cars;
+    st->n_spawners = (int)t.n_spawners;
+    st->next_car_id = (int)t.next_id;
+    st->car_tail = (int)t.tail;
   }
   return PGTG_OK;
 }
 
 
 // One env's cars in list order (empty slots skipped): a strided copy of its slots.
-static int host_read_cars(pgtg_handle* h, uint64_t env, const uint4& t, std::vector<PgtgCar>& cars) {
+static int host_read_cars(pgtg_handle* h, uint64_t env, const TrafState& t, std::vector<PgtgCar>& cars) {
   cars.clear();
-  const int tail = (int)t.z;
+  const int tail = (int)t.tail;
   if (tail == 0) return 0;
   const uint64_t N = h->n;
   std::vector<uint32_t> w0(tail), w1(tail, 0u), id(tail);
-  if (t.w & kTrafFresh) {  // initial traffic still in the env's staging block (patience 0, id = slot)
+  if (t.fresh) {  // initial traffic still in the env's staging block (patience 0, id = slot)
     HIPCHK(h, hipMemcpy(w0.data(), h->S.fresh + env * (uint64_t)h->S.fresh_dw, 4 * (size_t)tail, hipMemcpyDeviceToHost));
     for (int k = 0; k < tail; k++) id[k] = (uint32_t)k;
   } else {
@@ -5901,26 +5859,24 @@ static int host_read_cars(pgtg_handle* h, uint64_t env, const uint4& t, std::vec
     HIPCHK(h, hipMemcpy2D(id.data(), 4, h->S.car_id + env, N * 4, 4, tail, hipMemcpyDeviceToHost));
   }
   for (int k = 0; k < tail; k++) {
-    if (w0[k] & kCarEmpty) continue;
-    cars.push_back(PgtgCar{(int32_t)id[k], (int32_t)(w0[k] & 255u), (int32_t)((w0[k] >> 8) & 255u),
-                           (int32_t)((w0[k] >> 16) & 31u), (int32_t)((w0[k] >> 21) & 7u), (int32_t)w1[k],
-                           (int32_t)((w0[k] >> 24) & 3u)});
+    if (car_empty(w0[k])) continue;
+    cars.push_back(PgtgCar{(int32_t)id[k], car_x(w0[k]), car_y(w0[k]), car_route(w0[k]), car_profile(w0[k]),
+                           (int32_t)w1[k], car_delay(w0[k])});
   }
-  if ((int)cars.size() != (int)(t.x & 0xffffu)) return fail(h, PGTG_E_DEVICE, "car slots disagree with the car count");
+  if ((int)cars.size() != (int)t.n_cars) return fail(h, PGTG_E_DEVICE, "car slots disagree with the car count");
   return 0;
 }
 
 // One env's car list written packed into slots [0, n); the traffic record gets n cars, tail n and
 // next id `next_id`.
-static int host_write_cars(pgtg_handle* h, uint64_t env, uint4 t, const std::vector<PgtgCar>& cars, uint32_t next_id) {
+static int host_write_cars(pgtg_handle* h, uint64_t env, TrafState t, const std::vector<PgtgCar>& cars, uint32_t next_id) {
   const int n = (int)cars.size();
   if (n > h->hcfg.car_cap) return fail(h, PGTG_E_UNSUPPORTED, "more cars than the handle's car capacity");
   const uint64_t N = h->n;
   std::vector<uint32_t> w0(n), w1(n), id(n);
   for (int k = 0; k < n; k++) {
     const PgtgCar& q = cars[k];
-    w0[k] = (uint32_t)q.x | (uint32_t)q.y << 8 | (uint32_t)q.route << 16 | (uint32_t)q.profile << 21 |
-            (uint32_t)q.delay << 24;
+    w0[k] = car_pack(q.x, q.y, q.route, q.profile, q.delay);
     w1[k] = (uint32_t)q.patience;
     id[k] = (uint32_t)q.id;
   }
@@ -5929,11 +5885,11 @@ static int host_write_cars(pgtg_handle* h, uint64_t env, uint4 t, const std::vec
     HIPCHK(h, hipMemcpy2D(h->S.car_w1 + env, N * 4, w1.data(), 4, 4, n, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy2D(h->S.car_id + env, N * 4, id.data(), 4, 4, n, hipMemcpyHostToDevice));
   }
-  t.x = (t.x & 0xffff0000u) | (uint32_t)n;
-  t.y = next_id;
-  t.z = (uint32_t)n;
-  t.w = 0u;  // the slot rows hold the list (not fresh); the counters no longer match: rebuilt next launch
-  HIPCHK(h, hipMemcpy(h->S.traf + env, &t, sizeof t, hipMemcpyHostToDevice));
+  t.n_cars = t.tail = (uint32_t)n;
+  t.next_id = next_id;
+  t.fresh = 0u;  // the slot rows hold the list; the counters no longer match: rebuilt next launch
+  const Quad q = traf_pack(t, 0u);
+  HIPCHK(h, hipMemcpy(h->S.traf + env, &q, sizeof q, hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -5942,9 +5898,9 @@ int pgtg_get_cars(pgtg_handle* h, uint64_t env, PgtgCar* cars, int32_t cap, int3
   *n = 0;
   if (!h->hcfg.need_car) return PGTG_OK;
   if (int rc = host_sync(h)) return rc;
-  uint4 t;
+  TrafState t;
   if (int rc = read_traf(h, env, &t)) return rc;
-  *n = (int)(t.x & 0xffffu);
+  *n = (int)t.n_cars;
   if (cars && cap > 0 && *n > 0) {
     std::vector<PgtgCar> v;
     if (int rc = host_read_cars(h, env, t, v)) return rc;
@@ -5959,9 +5915,9 @@ int pgtg_get_map_plan(pgtg_handle* h, uint64_t env, int32_t* w, int32_t* h_, uin
   if (int rc = host_sync(h)) return rc;
   const DevCfg& c = h->hcfg;
   std::vector<uint16_t> p;
-  EnvRec r;
+  EnvView v;
   if (int rc = read_plan_row(h, env, p)) return rc;
-  HIPCHK(h, hipMemcpy(&r, h->S.rec + env, sizeof r, hipMemcpyDeviceToHost));
+  if (int rc = read_rec(h, env, &v)) return rc;
   *w = c.tw;
   *h_ = c.th;
   for (int t = 0; t < c.nt; t++) {
@@ -5970,13 +5926,12 @@ int pgtg_get_map_plan(pgtg_handle* h, uint64_t env, int32_t* w, int32_t* h_, uin
     otype[t] = (int8_t)(ot - 1);
     omask[t] = (int8_t)(ot ? (int)plan_omask(p[t]) : -1);
   }
-  uint32_t sg = r.b.x;
-  start3[0] = (int)(sg & 0xffu) % c.tw;
-  start3[1] = (int)(sg & 0xffu) / c.tw;
-  start3[2] = (int)((sg >> 8) & 0xffu);
-  goal3[0] = (int)((sg >> 16) & 0xffu) % c.tw;
-  goal3[1] = (int)((sg >> 16) & 0xffu) / c.tw;
-  goal3[2] = (int)(sg >> 24);
+  start3[0] = sg_start_tile(v.sg) % c.tw;
+  start3[1] = sg_start_tile(v.sg) / c.tw;
+  start3[2] = sg_start_dir(v.sg);
+  goal3[0] = sg_goal_tile(v.sg) % c.tw;
+  goal3[1] = sg_goal_tile(v.sg) / c.tw;
+  goal3[2] = sg_goal_dir(v.sg);
   return PGTG_OK;
 }
 
@@ -6037,12 +5992,13 @@ int pgtg_set_agent(pgtg_handle* h, uint64_t env, int32_t x, int32_t y, int32_t v
   if (!h || env >= h->n) return PGTG_E_INVALID;
   if (int rc = host_sync(h)) return rc;
   h->obs_current = false;
-  EnvRec r;
-  HIPCHK(h, hipMemcpy(&r, h->S.rec + env, sizeof r, hipMemcpyDeviceToHost));
-  r.a.x = ((uint32_t)x & 0xffffu) | ((uint32_t)y << 16);
-  r.a.y = ((uint32_t)vx & 0xffffu) | ((uint32_t)vy << 16);
-  HIPCHK(h, hipMemcpy(h->S.rec + env, &r, sizeof r, hipMemcpyHostToDevice));
-  return PGTG_OK;
+  EnvView v;
+  if (int rc = read_rec(h, env, &v)) return rc;
+  v.px = x;
+  v.py = y;
+  v.vx = vx;
+  v.vy = vy;
+  return write_rec(h, env, v);
 }
 
 // a car the host may place: on the map, one of the 20 routes and 5 driver profiles
@@ -6056,14 +6012,14 @@ int pgtg_add_car(pgtg_handle* h, uint64_t env, int32_t x, int32_t y, int32_t rou
   if (!car_ok(h->hcfg, x, y, route, profile)) return fail(h, PGTG_E_INVALID, "car outside the map or bad route/profile");
   if (int rc = host_sync(h)) return rc;
   h->obs_current = false;
-  uint4 t;
+  TrafState t;
   if (int rc = read_traf(h, env, &t)) return rc;
   std::vector<PgtgCar> v;
   if (int rc = host_read_cars(h, env, t, v)) return rc;
   if ((int)v.size() >= h->hcfg.car_cap) return fail(h, PGTG_E_UNSUPPORTED, "car capacity exhausted");
-  const uint32_t id = car_id < 0 ? t.y : (uint32_t)car_id;
+  const uint32_t id = car_id < 0 ? t.next_id : (uint32_t)car_id;
   v.push_back(PgtgCar{(int32_t)id, x, y, route, profile, 0, 0});
-  return host_write_cars(h, env, t, v, car_id < 0 ? t.y + 1u : t.y);
+  return host_write_cars(h, env, t, v, car_id < 0 ? t.next_id + 1u : t.next_id);
 }
 
 // ---- whole-batch state dump / load (bit-exact replay) ----------------------------------------
@@ -6152,7 +6108,7 @@ static std::vector<StateSection> state_sections(pgtg_handle* h) {
   slots(31, S.car_w0, (uint64_t)c.car_slots);
   slots(32, S.car_w1, (uint64_t)c.car_slots);
   slots(33, S.car_id, (uint64_t)c.car_slots);
-  rows(34, S.traf, sizeof(uint4));
+  rows(34, S.traf, sizeof(Quad));
   slots(36, S.occ, (uint64_t)c.nt * 4);
   rows(35, S.spawners, (uint64_t)S.sp_pitch * 2);
   rows(37, S.fresh, (uint64_t)S.fresh_dw * 4);
@@ -6402,20 +6358,20 @@ int pgtg_set_to_state(pgtg_handle* h, uint64_t env, int32_t x, int32_t y, int32_
       return fail(h, PGTG_E_INVALID, "car outside the map or bad route/profile");
   if (int rc = host_sync(h)) return rc;
   h->obs_current = false;
-  EnvRec r;
-  HIPCHK(h, hipMemcpy(&r, h->S.rec + env, sizeof r, hipMemcpyDeviceToHost));
-  r.a.x = ((uint32_t)x & 0xffffu) | ((uint32_t)y << 16);
-  r.a.y = ((uint32_t)vx & 0xffffu) | ((uint32_t)vy << 16);
-  uint32_t flags = (r.a.z >> 16) & 0xfu;
-  flags = flat_tire ? (flags | kFlagFlatTire) : (flags & ~kFlagFlatTire);
-  r.a.z = (r.a.z & 0xfff0ffffu) | (flags << 16);
-  HIPCHK(h, hipMemcpy(h->S.rec + env, &r, sizeof r, hipMemcpyHostToDevice));
+  EnvView ev;
+  if (int rc = read_rec(h, env, &ev)) return rc;
+  ev.px = x;
+  ev.py = y;
+  ev.vx = vx;
+  ev.vy = vy;
+  ev.flags = flat_tire ? (ev.flags | kFlagFlatTire) : (ev.flags & ~kFlagFlatTire);
+  if (int rc = write_rec(h, env, ev)) return rc;
   if (c.need_car) {
-    uint4 t;
+    TrafState t;
     if (int rc = read_traf(h, env, &t)) return rc;
     std::vector<PgtgCar> v;
     for (int k = 0; k < n_cars; k++) v.push_back(PgtgCar{cars[k].id, cars[k].x, cars[k].y, cars[k].route, cars[k].profile, 0, 0});
-    if (int rc = host_write_cars(h, env, t, v, n_cars > 0 ? (uint32_t)cars[n_cars - 1].id + 1u : t.y)) return rc;
+    if (int rc = host_write_cars(h, env, t, v, n_cars > 0 ? (uint32_t)cars[n_cars - 1].id + 1u : t.next_id)) return rc;
   }
   return PGTG_OK;
 }

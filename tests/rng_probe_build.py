@@ -11,7 +11,8 @@ from pgtg_amd import build as B
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "rng_probe.hip")
-DEPS = [SRC, os.path.join(B.PKG, "csrc", "pgtg_device.h"), os.path.join(os.path.dirname(B.PKG), "include", "pgtg.h")]
+DEPS = [SRC, os.path.join(B.PKG, "csrc", "pgtg_device.h"), os.path.join(B.PKG, "csrc", "pgtg_records.h"),
+        os.path.join(os.path.dirname(B.PKG), "include", "pgtg.h")]
 OUT = os.path.join(B.PKG, "librng_probe.so")
 
 
