@@ -491,6 +491,78 @@ int pgtg_ppo_step(pgtg_handle* h, const PgtgPpoStep* a);
  * normalise a batch of one), steps or n of 0, steps * n overflowing: PGTG_E_INVALID, nothing is launched. */
 int pgtg_ppo_adv_stats(pgtg_handle* h, const void* advantages, const void* indices, uint64_t batch, uint64_t steps,
                        uint64_t n, float* out);
+/* The rest of SB3's PPO.train (new): value-function clipping, target_kl without a host synchronisation per
+ * minibatch, the train log and the epoch's permutation.  The three _ex entry points take the call they extend
+ * and a PgtgPpoExtra; extra == NULL is exactly that call (pgtg_ppo_grad, pgtg_ppo_step and pgtg_ppo_adv_stats
+ * call them so), and so is an extra of zeros.
+ *   PGTG_PPO_CLIP_VF (pgtg_ppo_grad_ex): with v0 = old_values[step][env] (required; the rollout's values) and
+ *     c = clip_range_vf, value_loss = mean((returns - (v0 + clamp(value - v0, -c, c)))^2), whose derivative with
+ *     respect to value is that of the unclipped term where -c <= value - v0 <= c (boundaries included, as
+ *     torch.clamp's) and 0 elsewhere.  Only the value tower's gradients, value_loss and loss change.
+ *   stop_at (device uint32, the update's stop word: 0 when the update starts) with ordinal = m, the place
+ *     1, 2, ... of the minibatch within the update, is the gate: a kernel of pgtg_ppo_adv_stats_ex or
+ *     pgtg_ppo_grad_ex returns at once when stop_at != 0 && stop_at < m, one of pgtg_ppo_step_ex when
+ *     stop_at != 0 && stop_at <= m, having written nothing (gradients, stats, parameters, moments, packed and
+ *     grad_norm keep their contents).  The host launches every minibatch and reads stop_at once, at the end.
+ *   PGTG_PPO_TARGET_KL (pgtg_ppo_grad_ex; stop_at required): the thread that writes stats stores stop_at = m
+ *     when stop_at == 0 and approx_kl > 1.5f * (float)target_kl (a float32 compare; NaN compares false).  That
+ *     minibatch has written its gradients and stats and takes no step: SB3's break before optimizer.step().
+ *     No kernel is gated by a value its own launch writes, so the outcome does not depend on the order in
+ *     which workgroups run.
+ * clip_range_vf or target_kl negative or non-finite, PGTG_PPO_CLIP_VF without old_values, PGTG_PPO_TARGET_KL
+ * without stop_at, stop_at with ordinal == 0 or not 4-byte aligned, unknown flags: PGTG_E_INVALID, nothing launched. */
+#define PGTG_PPO_CLIP_VF 1u
+#define PGTG_PPO_TARGET_KL 2u
+typedef struct {
+  uint32_t flags;            /* PGTG_PPO_CLIP_VF | PGTG_PPO_TARGET_KL */
+  uint32_t ordinal;          /* m = 1, 2, ...; read when stop_at is set */
+  const float* old_values;   /* [steps][n] */
+  double clip_range_vf, target_kl;
+  uint32_t* stop_at;         /* device; NULL: no gate */
+} PgtgPpoExtra;
+int pgtg_ppo_grad_ex(pgtg_handle* h, const PgtgPpoGrad* a, const PgtgPpoExtra* extra);
+int pgtg_ppo_step_ex(pgtg_handle* h, const PgtgPpoStep* a, const PgtgPpoExtra* extra);
+int pgtg_ppo_adv_stats_ex(pgtg_handle* h, const void* advantages, const void* indices, uint64_t batch, uint64_t steps,
+                          uint64_t n, float* out, const PgtgPpoExtra* extra);
+/* out[2] (device, float32) = {1 - r, r} with r = var(returns - values) / var(returns) over count float32 values
+ * each (a rollout's [steps][n] arrays, contiguous): SB3's explained_variance(values.flatten(),
+ * returns.flatten()) and the ratio it is one minus (which keeps its relative precision when the value function
+ * is good).  Population variances in two passes (the means, then the squared deviations), in fp64; both NaN
+ * when var(returns) == 0.  Three launches (k_ppo_expl_var), asynchronous on the handle's stream; the partition
+ * depends on count alone and every sum runs in a fixed order: two calls give the same bits.  workspace:
+ * pgtg_ppo_expl_var_workspace_bytes() bytes, 8-byte aligned, contents irrelevant.  A NULL pointer, count == 0 or
+ * above 2^40, a workspace not 8-byte or out not 4-byte aligned: PGTG_E_INVALID, nothing launched. */
+int pgtg_ppo_expl_var_workspace_bytes(uint64_t* bytes);
+int pgtg_ppo_expl_var(pgtg_handle* h, const float* values, const float* returns, uint64_t count, void* workspace,
+                      float* out);
+/* The train log of one update from the [minibatches][8] statistics rows its pgtg_ppo_grad calls wrote (one
+ * launch, k_ppo_log, asynchronous on the handle's stream).  With run = stop_at's value where stop_at is given
+ * and non-zero, else minibatches: the means over rows [0, run) of entropy, policy and value loss and of the clip
+ * fraction; approx_kl's mean over the rows of the last run epoch only, [(run - 1) / per_epoch * per_epoch, run)
+ * (SB3 resets that list per epoch); loss of row run - 1; epochs = (run - 1) / per_epoch + 1, SB3's _n_updates
+ * increment; every mean an fp64 sum in row order, rounded to float32 once.  expl_var: pgtg_ppo_expl_var's out or
+ * NULL (NaN).  minibatches == 0 gives NaNs and zeros.  stats or out NULL, stats not 16-byte aligned, out,
+ * stop_at or expl_var not 4-byte aligned, per_epoch == 0, minibatches above 2^31: PGTG_E_INVALID, nothing
+ * launched. */
+typedef struct {
+  uint32_t minibatches;      /* run */
+  uint32_t epochs;
+  uint32_t early_stop;       /* stop_at was set */
+  uint32_t reserved;
+  float entropy_loss, policy_gradient_loss, value_loss, clip_fraction, approx_kl, loss;
+  float explained_variance, variance_ratio;
+} PgtgPpoLog;
+int pgtg_ppo_log(pgtg_handle* h, const float* stats, uint64_t minibatches, uint64_t per_epoch, const uint32_t* stop_at,
+                 const float* expl_var, PgtgPpoLog* out);
+/* perm[total] (device, int64) = a permutation of [0, total) that is a function of (total, seed, counter) alone
+ * (one launch, k_ppo_perm, asynchronous on the handle's stream): an alternating Feistel network of six rounds
+ * over ceil(log2 total) bits, round function the splitmix64 finaliser of pgtg_policy's uniform draw in a domain
+ * of its own, cycle-walked into [0, total).  Every element is computed on its own: no sort, no atomics, no
+ * dependence on the grid.  An element whose walk exceeds 64 steps (probability below 2^-64) is written as its own
+ * index and sets the handle's error byte (element mod batch size) to -PGTG_E_DEVICE (pgtg_error_count).
+ * pgtg_amd.rollout.permutation_reference restates it.  perm NULL or not 8-byte aligned, total == 0 or above
+ * 2^38: PGTG_E_INVALID, nothing launched. */
+int pgtg_ppo_perm(pgtg_handle* h, uint64_t total, uint64_t seed, uint64_t counter, int64_t* perm);
 /* Policy evaluation with per-env episode quotas (new; ModularEvaluator.evaluate of pgtg/evaluator.py:284-339
  * for the batch, counted as SB3's evaluate_policy counts a vector env: env e contributes its first
  * quota_e = (n_episodes + e) / n episodes (integer division; the quotas sum to n_episodes), so short episodes

@@ -38,6 +38,8 @@ EXPORTED = [
     "pgtg_policy", "pgtg_policy_pack", "pgtg_policy_packed_bytes", "pgtg_policy_chunk",
     "pgtg_ppo_workspace_bytes", "pgtg_ppo_grad",
     "pgtg_ppo_step_workspace_bytes", "pgtg_ppo_step", "pgtg_ppo_adv_stats",
+    "pgtg_ppo_grad_ex", "pgtg_ppo_step_ex", "pgtg_ppo_adv_stats_ex",
+    "pgtg_ppo_expl_var_workspace_bytes", "pgtg_ppo_expl_var", "pgtg_ppo_log", "pgtg_ppo_perm",
     "pgtg_snapshot_create", "pgtg_snapshot_destroy", "pgtg_snapshot_bytes", "pgtg_snapshot_save", "pgtg_snapshot_load",
 ]
 
@@ -159,6 +161,20 @@ class PgtgPpoStep(C.Structure):
                 ("max_grad_norm", C.c_float), ("grad_norm", C.c_void_p)]
 
 
+PGTG_PPO_CLIP_VF, PGTG_PPO_TARGET_KL = 1, 2
+
+
+class PgtgPpoExtra(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("ordinal", C.c_uint32), ("old_values", C.c_void_p),
+                ("clip_range_vf", C.c_double), ("target_kl", C.c_double), ("stop_at", C.c_void_p)]
+
+
+class PgtgPpoLog(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("minibatches", "epochs", "early_stop", "reserved")] + [
+        (n, C.c_float) for n in ("entropy_loss", "policy_gradient_loss", "value_loss", "clip_fraction", "approx_kl",
+                                 "loss", "explained_variance", "variance_ratio")]
+
+
 _lib = None
 
 
@@ -222,6 +238,13 @@ def lib():
         "pgtg_ppo_step_workspace_bytes": ([u64, C.POINTER(u64)], C.c_int),
         "pgtg_ppo_step": ([vp, C.POINTER(PgtgPpoStep)], C.c_int),
         "pgtg_ppo_adv_stats": ([vp, vp, vp, u64, u64, u64, vp], C.c_int),
+        "pgtg_ppo_grad_ex": ([vp, C.POINTER(PgtgPpoGrad), C.POINTER(PgtgPpoExtra)], C.c_int),
+        "pgtg_ppo_step_ex": ([vp, C.POINTER(PgtgPpoStep), C.POINTER(PgtgPpoExtra)], C.c_int),
+        "pgtg_ppo_adv_stats_ex": ([vp, vp, vp, u64, u64, u64, vp, C.POINTER(PgtgPpoExtra)], C.c_int),
+        "pgtg_ppo_expl_var_workspace_bytes": ([C.POINTER(u64)], C.c_int),
+        "pgtg_ppo_expl_var": ([vp, vp, vp, u64, vp, vp], C.c_int),
+        "pgtg_ppo_log": ([vp, vp, u64, u64, vp, vp, vp], C.c_int),
+        "pgtg_ppo_perm": ([vp, u64, u64, u64, vp], C.c_int),
         "pgtg_snapshot_create": ([vp, u64, C.POINTER(vp)], C.c_int),
         "pgtg_snapshot_destroy": ([vp], C.c_int),
         "pgtg_snapshot_bytes": ([vp, C.POINTER(u64), C.POINTER(u64)], C.c_int),

@@ -32,6 +32,7 @@
 #include "pgtg_policy.h"
 #include "pgtg_ppo.h"
 #include "pgtg_ppo_step.h"
+#include "pgtg_ppo_log.h"
 #include "pgtg_snapshot.h"
 
 namespace pgtg {
@@ -6728,7 +6729,33 @@ int pgtg_ppo_workspace_bytes(uint64_t obs_dim, uint64_t batch, uint64_t* bytes) 
   return PGTG_OK;
 }
 
-int pgtg_ppo_grad(pgtg_handle* h, const PgtgPpoGrad* a) {
+// The refusals of a PgtgPpoExtra, under the entry point's name `fn`; reads_flags: `fn` is the one that reads
+// clip_range_vf and target_kl (the others take the gate alone)
+static int check_extra(pgtg_handle* h, const char* fn, const PgtgPpoExtra* x, bool reads_flags) {
+  if (!x) return PGTG_OK;
+  const std::string f(fn);
+  if (x->flags & ~(PGTG_PPO_CLIP_VF | PGTG_PPO_TARGET_KL)) return fail(h, PGTG_E_INVALID, f + ": unknown flags in extra");
+  if (reads_flags && (x->flags & PGTG_PPO_CLIP_VF)) {
+    if (!(std::isfinite(x->clip_range_vf) && x->clip_range_vf >= 0.0))
+      return fail(h, PGTG_E_INVALID, f + ": clip_range_vf must be finite and at least 0");
+    if (!x->old_values) return fail(h, PGTG_E_INVALID, f + ": clip_range_vf needs old_values");
+    if ((uintptr_t)x->old_values & 3u) return fail(h, PGTG_E_INVALID, f + ": old_values must be 4-byte aligned");
+  }
+  if (reads_flags && (x->flags & PGTG_PPO_TARGET_KL)) {
+    if (!(std::isfinite(x->target_kl) && x->target_kl >= 0.0))
+      return fail(h, PGTG_E_INVALID, f + ": target_kl must be finite and at least 0");
+    if (!x->stop_at) return fail(h, PGTG_E_INVALID, f + ": target_kl needs stop_at");
+  }
+  if (x->stop_at) {
+    if ((uintptr_t)x->stop_at & 3u) return fail(h, PGTG_E_INVALID, f + ": stop_at must be 4-byte aligned");
+    if (x->ordinal == 0) return fail(h, PGTG_E_INVALID, f + ": ordinal counts from 1 where stop_at is set");
+  }
+  return PGTG_OK;
+}
+
+int pgtg_ppo_grad(pgtg_handle* h, const PgtgPpoGrad* a) { return pgtg_ppo_grad_ex(h, a, nullptr); }
+
+int pgtg_ppo_grad_ex(pgtg_handle* h, const PgtgPpoGrad* a, const PgtgPpoExtra* x) {
   if (!h) return PGTG_E_INVALID;
   if (!a) return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: no arguments");
   if (int e = check_obs_dim(h, "pgtg_ppo_grad", a->obs_dim)) return e;
@@ -6748,6 +6775,7 @@ int pgtg_ppo_grad(pgtg_handle* h, const PgtgPpoGrad* a) {
     return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: batch * obs_dim overflows");
   if (!std::isfinite(a->clip_range) || !std::isfinite(a->ent_coef) || !std::isfinite(a->vf_coef))
     return fail(h, PGTG_E_INVALID, "pgtg_ppo_grad: clip_range, ent_coef and vf_coef must be finite");
+  if (int e = check_extra(h, "pgtg_ppo_grad_ex", x, true)) return e;
   if (a->batch == 0) return PGTG_OK;
   const PpoPlan pl = ppo_plan(a->batch, a->obs_dim);
   const uint64_t rgrid = (128 * a->obs_dim + kPpoSlot + kPpoThreads - 1) / kPpoThreads;
@@ -6777,6 +6805,13 @@ int pgtg_ppo_grad(pgtg_handle* h, const PgtgPpoGrad* a) {
   p.err_n = h->S.err ? h->n : 0;
   put12(p.g, a->grads);
   p.stats = a->stats;
+  const bool clip_vf = x && (x->flags & PGTG_PPO_CLIP_VF), kl = x && (x->flags & PGTG_PPO_TARGET_KL);
+  p.old_values = clip_vf ? x->old_values : nullptr;
+  p.clip_vf = clip_vf ? (float)x->clip_range_vf : 0.f;
+  p.stop_at = x ? x->stop_at : nullptr;
+  p.ordinal = x && x->stop_at ? x->ordinal : 0;
+  p.has_kl = kl ? 1u : 0u;
+  p.kl_limit = kl ? 1.5f * (float)x->target_kl : 0.f;
   HIPCHK(h, hipSetDevice(h->device));
   hipLaunchKernelGGL(k_ppo_loss, dim3((unsigned)pl.blocks), dim3(kPpoThreads), 0, h->stream, p);
   hipLaunchKernelGGL(k_ppo_dw1, dim3((unsigned)pl.dtiles, (unsigned)pl.segs), dim3(kPpoThreads), 0, h->stream, p);
@@ -6806,7 +6841,9 @@ static double widen_decimal(float x) {
   return x;
 }
 
-int pgtg_ppo_step(pgtg_handle* h, const PgtgPpoStep* a) {
+int pgtg_ppo_step(pgtg_handle* h, const PgtgPpoStep* a) { return pgtg_ppo_step_ex(h, a, nullptr); }
+
+int pgtg_ppo_step_ex(pgtg_handle* h, const PgtgPpoStep* a, const PgtgPpoExtra* x) {
   if (!h) return PGTG_E_INVALID;
   if (!a) return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: no arguments");
   if (int e = check_obs_dim(h, "pgtg_ppo_step", a->obs_dim)) return e;
@@ -6822,7 +6859,10 @@ int pgtg_ppo_step(pgtg_handle* h, const PgtgPpoStep* a) {
     return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: beta1 and beta2 must be in [0, 1)");
   if (!(a->max_grad_norm > 0.f))
     return fail(h, PGTG_E_INVALID, "pgtg_ppo_step: max_grad_norm must be above 0 (+inf: no clip)");
+  if (int e = check_extra(h, "pgtg_ppo_step_ex", x, false)) return e;
   PpoStepArgs p;
+  p.stop_at = x ? x->stop_at : nullptr;
+  p.ordinal = x && x->stop_at ? x->ordinal : 0;
   put12(p.p, a->params);
   put12(p.g, a->grads);
   put12(p.m, a->exp_avg);
@@ -6852,15 +6892,86 @@ int pgtg_ppo_step(pgtg_handle* h, const PgtgPpoStep* a) {
 
 int pgtg_ppo_adv_stats(pgtg_handle* h, const void* advantages, const void* indices, uint64_t batch, uint64_t steps,
                        uint64_t n, float* out) {
+  return pgtg_ppo_adv_stats_ex(h, advantages, indices, batch, steps, n, out, nullptr);
+}
+
+int pgtg_ppo_adv_stats_ex(pgtg_handle* h, const void* advantages, const void* indices, uint64_t batch, uint64_t steps,
+                          uint64_t n, float* out, const PgtgPpoExtra* x) {
   if (!h) return PGTG_E_INVALID;
   if (!advantages || !indices || !out)
     return fail(h, PGTG_E_INVALID, "pgtg_ppo_adv_stats: advantages, indices and out are required");
   if (batch < 2) return fail(h, PGTG_E_INVALID, "pgtg_ppo_adv_stats: batch must be at least 2 (the unbiased std)");
   if (steps == 0 || n == 0) return fail(h, PGTG_E_INVALID, "pgtg_ppo_adv_stats: steps and n must be at least 1");
   if (steps > (UINT64_MAX >> 3) / n) return fail(h, PGTG_E_INVALID, "pgtg_ppo_adv_stats: steps * n overflows");
-  AdvStatsArgs p = {(const float*)advantages, (const int64_t*)indices, batch, steps, n, out};
+  if (int e = check_extra(h, "pgtg_ppo_adv_stats_ex", x, false)) return e;
+  AdvStatsArgs p = {(const float*)advantages, (const int64_t*)indices, batch, steps, n, out, x ? x->stop_at : nullptr,
+                    x && x->stop_at ? x->ordinal : 0};
   HIPCHK(h, hipSetDevice(h->device));
   hipLaunchKernelGGL(k_ppo_adv_stats, dim3(1), dim3(kAdvThreads), 0, h->stream, p);
+  HIPCHK(h, hipGetLastError());
+  return PGTG_OK;
+}
+
+// The explained variance, the log and the permutation of an update (pgtg_ppo_log.h)
+int pgtg_ppo_expl_var_workspace_bytes(uint64_t* bytes) {
+  if (!bytes) return PGTG_E_INVALID;
+  *bytes = 4 * (uint64_t)kEvMaxBlocks * sizeof(double);
+  return PGTG_OK;
+}
+
+int pgtg_ppo_expl_var(pgtg_handle* h, const float* values, const float* returns, uint64_t count, void* workspace,
+                      float* out) {
+  if (!h) return PGTG_E_INVALID;
+  if (!values || !returns || !workspace || !out)
+    return fail(h, PGTG_E_INVALID, "pgtg_ppo_expl_var: values, returns, workspace and out are required");
+  if (count == 0 || count > (1ull << 40)) return fail(h, PGTG_E_INVALID, "pgtg_ppo_expl_var: count must be in [1, 2^40]");
+  if (((uintptr_t)values | (uintptr_t)returns | (uintptr_t)out) & 3u)
+    return fail(h, PGTG_E_INVALID, "pgtg_ppo_expl_var: values, returns and out must be 4-byte aligned");
+  if ((uintptr_t)workspace & 7u) return fail(h, PGTG_E_INVALID, "pgtg_ppo_expl_var: workspace must be 8-byte aligned");
+  ExplVarArgs p = {values, returns, count, (double*)workspace, out};
+  const dim3 g((unsigned)ev_blocks(count)), b(kEvThreads);
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_ppo_expl_var<0>, g, b, 0, h->stream, p);
+  hipLaunchKernelGGL(k_ppo_expl_var<1>, g, b, 0, h->stream, p);
+  hipLaunchKernelGGL(k_ppo_expl_var<2>, dim3(1), b, 0, h->stream, p);
+  HIPCHK(h, hipGetLastError());
+  return PGTG_OK;
+}
+
+int pgtg_ppo_log(pgtg_handle* h, const float* stats, uint64_t minibatches, uint64_t per_epoch, const uint32_t* stop_at,
+                 const float* expl_var, PgtgPpoLog* out) {
+  if (!h) return PGTG_E_INVALID;
+  if (!stats || !out) return fail(h, PGTG_E_INVALID, "pgtg_ppo_log: stats and out are required");
+  if ((uintptr_t)stats & 15u) return fail(h, PGTG_E_INVALID, "pgtg_ppo_log: stats must be 16-byte aligned");
+  if (((uintptr_t)out | (uintptr_t)stop_at | (uintptr_t)expl_var) & 3u)
+    return fail(h, PGTG_E_INVALID, "pgtg_ppo_log: out, stop_at and expl_var must be 4-byte aligned");
+  if (per_epoch == 0) return fail(h, PGTG_E_INVALID, "pgtg_ppo_log: per_epoch must be at least 1");
+  if (minibatches > (1ull << 31)) return fail(h, PGTG_E_INVALID, "pgtg_ppo_log: minibatches beyond 2^31");
+  PpoLogArgs p = {stats, minibatches, per_epoch, stop_at, expl_var, out};
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_ppo_log, dim3(1), dim3(64), 0, h->stream, p);
+  HIPCHK(h, hipGetLastError());
+  return PGTG_OK;
+}
+
+int pgtg_ppo_perm(pgtg_handle* h, uint64_t total, uint64_t seed, uint64_t counter, int64_t* perm) {
+  if (!h) return PGTG_E_INVALID;
+  if (!perm) return fail(h, PGTG_E_INVALID, "pgtg_ppo_perm: perm is required");
+  if ((uintptr_t)perm & 7u) return fail(h, PGTG_E_INVALID, "pgtg_ppo_perm: perm must be 8-byte aligned");
+  if (total == 0 || total > (1ull << 38)) return fail(h, PGTG_E_INVALID, "pgtg_ppo_perm: total must be in [1, 2^38]");
+  uint32_t bits = 0;
+  while ((1ull << bits) < total) bits++;  // ceil(log2 total)
+  PermArgs p;
+  p.perm = perm;
+  p.total = total;
+  p.key = seed ^ (counter * 0x9E3779B97F4A7C15ull) ^ 0x70706F5F7065726Dull;
+  p.lo_bits = bits / 2;
+  p.hi_bits = bits - bits / 2;
+  p.err = h->S.err;
+  p.err_n = h->S.err ? h->n : 0;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_ppo_perm, dim3((unsigned)((total + kPermThreads - 1) / kPermThreads)), dim3(kPermThreads), 0,
+                     h->stream, p);
   HIPCHK(h, hipGetLastError());
   return PGTG_OK;
 }

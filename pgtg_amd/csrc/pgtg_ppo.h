@@ -1,4 +1,4 @@
-// pgtg_ppo.h -- one PPO minibatch of SB3's PPO.train (defaults, clip_range_vf = None) over a finished
+// pgtg_ppo.h -- one PPO minibatch of SB3's PPO.train (clip_range_vf optional) over a finished
 // rollout's int8 rows: the loss, its six statistics and the gradient with respect to the twelve MlpPolicy
 // tensors (include/pgtg.h pgtg_ppo_grad).  Three kernels and no floating-point atomic:
 //   k_ppo_loss    64 samples per workgroup: gathers their rows, runs k_policy's forward and heads (the functions
@@ -64,7 +64,24 @@ struct PpoArgs {
   uint64_t err_n;
   PolicyTensors<float> g;
   float* stats;
+  // pgtg_ppo_grad_ex's extras, all absent (NULL, 0) from pgtg_ppo_grad
+  const float* old_values;  // value clipping: SB3's clip_range_vf over the rollout's values; NULL: none
+  float clip_vf;
+  uint32_t* stop_at;        // the update's stop word (target_kl); NULL: no gate
+  uint32_t ordinal;         // this minibatch's place m = 1, 2, ... within the update
+  uint32_t has_kl;          // k_ppo_reduce stores stop_at = m once approx_kl > kl_limit
+  float kl_limit;           // 1.5f * target_kl
 };
+
+// The gate of an update with target_kl: the launch set of minibatch m does nothing once an earlier minibatch
+// has stopped the update (stop_at < m), and its optimiser step nothing from the stopping minibatch on
+// (stop_at <= m).  One uniform load; no kernel is gated by a value written in its own launch (k_ppo_reduce of
+// ordinal m stores m, which gates neither itself nor its own k_ppo_loss and k_ppo_dw1).
+__device__ __forceinline__ bool ppo_gated(const uint32_t* stop_at, uint32_t ordinal, bool step) {
+  if (!stop_at) return false;
+  const uint32_t s = *stop_at;
+  return s != 0 && (step ? s <= ordinal : s < ordinal);
+}
 
 // Sample idx of a rollout of T steps of N envs (SB3's flat order, env-major): its env and its step; false for
 // an index outside [0, T N), which no kernel dereferences.
@@ -107,6 +124,7 @@ __global__ void __launch_bounds__(kPpoThreads) k_ppo_loss(PpoArgs a) {
   float* h1 = lds;
   float* h2 = lds + kPpoRows * kPolHPitch;
   static_assert(kPpoRows == kPolRows && kPpoThreads == kPolThreads, "k_policy's tiling");
+  if (ppo_gated(a.stop_at, a.ordinal, false)) return;
 
   const uint32_t tid = threadIdx.x, w = tid >> 6;
   const uint64_t D = a.D, B = a.B, blk = blockIdx.x;
@@ -173,11 +191,17 @@ __global__ void __launch_bounds__(kPpoThreads) k_ppo_loss(PpoArgs a) {
         const float p1 = adv * ratio, p2 = adv * rc;
         const bool through = p1 < p2 || (ratio >= a.clip_lo && ratio <= a.clip_hi);
         const float gr = through ? -adv * ratio : 0.f;  // d policy term / d logp
-        const float dv = a.ret[so] - val;
+        float dv = a.ret[so] - val;
+        bool vthrough = true;
+        if (a.old_values) {  // values_pred = old + clamp(value - old, -c, c): torch's clamp passes the closed interval,
+          const float ov = a.old_values[so], dd = val - ov;  // where values_pred is the value itself
+          vthrough = dd >= -a.clip_vf && dd <= a.clip_vf;
+          if (!vthrough) dv = a.ret[so] - (ov + fminf(fmaxf(dd, -a.clip_vf), a.clip_vf));
+        }
 #pragma unroll
         for (int c = 0; c < kPolAct; c++)
           dl[c] = (gr * ((act == c ? 1.f : 0.f) - p[c]) + a.ent_coef * (p[c] * (lp[c] + ent))) * inv_b;
-        dl[kPolAct] = a.vf_coef * (-2.f * dv) * inv_b;
+        dl[kPolAct] = vthrough ? a.vf_coef * (-2.f * dv) * inv_b : 0.f;
         st[0] = -fminf(p1, p2);
         st[1] = dv * dv;
         st[2] = -ent;
@@ -289,6 +313,7 @@ __global__ void __launch_bounds__(kPpoThreads) k_ppo_dw1(PpoArgs a) {
   const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const uint32_t n16 = lane & 15, q = lane >> 4;
   const uint64_t D = a.D, B = a.B;
+  if (ppo_gated(a.stop_at, a.ordinal, false)) return;
   const PpoPlan pl = ppo_plan(B, D);
   const uint64_t k0 = (uint64_t)blockIdx.x * kPpoDTile, seg = blockIdx.y;
   const uint64_t blk0 = seg * pl.seg_blocks;
@@ -359,6 +384,8 @@ __global__ void __launch_bounds__(kPpoThreads) k_ppo_dw1(PpoArgs a) {
 
 __global__ void __launch_bounds__(kPpoThreads) k_ppo_reduce(PpoArgs a) {
   const uint64_t D = a.D, B = a.B;
+  const uint32_t stop = a.stop_at ? *a.stop_at : 0;  // (this launch alone may store it, and stores a.ordinal)
+  if (stop != 0 && stop < a.ordinal) return;
   const PpoPlan pl = ppo_plan(B, D);
   const uint64_t gid = (uint64_t)blockIdx.x * kPpoThreads + threadIdx.x;
   if (gid < 128 * D) {
@@ -383,6 +410,7 @@ __global__ void __launch_bounds__(kPpoThreads) k_ppo_reduce(PpoArgs a) {
     a.stats[5] = m[4];
     a.stats[6] = 0.f;
     a.stats[7] = 0.f;
+    if (a.has_kl && stop == 0 && m[3] > a.kl_limit) *a.stop_at = a.ordinal;  // (a NaN compares false, as in torch)
     return;
   }
   float* dst;

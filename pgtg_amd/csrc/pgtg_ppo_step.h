@@ -43,6 +43,8 @@ struct PpoStepArgs {
   float step_size, bc2_sqrt;  // lr / (1 - beta1^step), sqrt(1 - beta2^step): in double on the host, rounded once
   float w1, beta2, w2, eps;   // 1 - beta1, beta2, 1 - beta2
   float max_norm;
+  const uint32_t* stop_at;  // pgtg_ppo_step_ex's gate (pgtg_ppo.h ppo_gated); NULL: none
+  uint32_t ordinal;
 };
 
 // element i of the twelve tensors end to end (step_params' order): its tensor and its offset there
@@ -77,6 +79,7 @@ __device__ __forceinline__ double step_tree(double* red, uint32_t tid) {
 __global__ void __launch_bounds__(kStepThreads) k_ppo_gnorm(PpoStepArgs a) {
   __shared__ double red[kStepThreads];
   const uint64_t D = a.D, n = step_params(D);
+  if (ppo_gated(a.stop_at, a.ordinal, true)) return;
   const uint64_t stride = (uint64_t)gridDim.x * kStepThreads;
   double s[kStepSets] = {0.0, 0.0, 0.0, 0.0};
   for (uint64_t i0 = (uint64_t)blockIdx.x * kStepThreads + threadIdx.x; i0 < n; i0 += kStepSets * stride)
@@ -99,6 +102,7 @@ __global__ void __launch_bounds__(kStepThreads) k_ppo_adam(PpoStepArgs a) {
   __shared__ double red[kStepMaxBlocks];
   static_assert(kStepMaxBlocks == kStepThreads, "one partial per thread");
   const uint64_t D = a.D;
+  if (ppo_gated(a.stop_at, a.ordinal, true)) return;
   const PolicyLayout L = policy_layout(D);
   red[threadIdx.x] = threadIdx.x < step_blocks(D) ? a.ws[threadIdx.x] : 0.0;
   const float total = (float)sqrt(step_tree<kStepMaxBlocks>(red, threadIdx.x));
@@ -132,6 +136,8 @@ struct AdvStatsArgs {
   const int64_t* indices;
   uint64_t B, T, N;
   float* out;
+  const uint32_t* stop_at;  // pgtg_ppo_adv_stats_ex's gate; NULL: none
+  uint32_t ordinal;
 };
 
 // the advantage of batch position s; an index outside the rollout stands as 0
@@ -144,6 +150,7 @@ __global__ void __launch_bounds__(kAdvThreads) k_ppo_adv_stats(AdvStatsArgs a) {
   __shared__ double red[kAdvThreads];
   const uint32_t tid = threadIdx.x;
   const uint64_t B = a.B;
+  if (ppo_gated(a.stop_at, a.ordinal, false)) return;
   double s[kStepSets] = {0.0, 0.0, 0.0, 0.0};
   for (uint64_t i0 = tid; i0 < B; i0 += kStepSets * kAdvThreads)
 #pragma unroll

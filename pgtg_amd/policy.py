@@ -129,12 +129,27 @@ def _host(t):
 STAT_NAMES = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction")
 
 
+def check_clip_range_vf(clip_range_vf):
+    """clip_range_vf as a float, or None; ValueError for a negative or non-finite one."""
+    if clip_range_vf is None:
+        return None
+    c = float(clip_range_vf)
+    if not (math.isfinite(c) and c >= 0.0):
+        raise ValueError("clip_range_vf must be finite and at least 0 (None: no value clipping)")
+    return c
+
+
 def ppo_terms(state_dict, obs_int8, actions, old_log_probs, advantages, returns, clip_range, ent_coef, vf_coef,
-              normalize, dtype=np.float64) -> dict:
+              normalize, dtype=np.float64, clip_range_vf=None, old_values=None) -> dict:
     """Every intermediate of one PPO minibatch at precision dtype (ppo_reference's working; the tests take the
     accumulated magnitudes from it): the layers' inputs `x, h1p, h2p, h1v, h2v`, the derivatives of the loss
     with respect to the layers' pre-activations `dz1p, dz2p, dlogits, dz1v, dz2v, dvalue` (already divided
-    by B), and the per-sample terms of the statistics `t_policy, t_value, t_entropy, ratio, log_ratio, clipped`."""
+    by B), and the per-sample terms of the statistics `t_policy, t_value, t_entropy, ratio, log_ratio, clipped`.
+    clip_range_vf with old_values [B]: SB3's value clipping, values_pred = old_values + clamp(value - old_values,
+    -c, c) in the value loss; the clamp passes the gradient on the closed interval, as torch's does."""
+    clip_range_vf = check_clip_range_vf(clip_range_vf)
+    if clip_range_vf is not None and old_values is None:
+        raise ValueError("clip_range_vf needs old_values")
     x = np.asarray(obs_int8)
     if x.dtype != np.int8 or x.ndim != 2:
         raise ValueError("obs_int8: an int8 [B, D] array")
@@ -167,14 +182,21 @@ def ppo_terms(state_dict, obs_int8, actions, old_log_probs, advantages, returns,
     onehot = np.zeros_like(p)
     onehot[ar, act] = 1
     dlogits = (g_logp[:, None] * (onehot - p) + ec * (p * (lsm + entropy[:, None]))) / dtype(B)
-    dvalue = vc * (-2 * (ret - value)) / dtype(B)
+    value_pred, v_through = value, np.ones(B, dtype=bool)
+    if clip_range_vf is not None:
+        cv, ov = dtype(clip_range_vf), np.asarray(_host(old_values), dtype=dtype).reshape(B)
+        dd = value - ov
+        v_through = (dd >= -cv) & (dd <= cv)
+        value_pred = np.where(v_through, value, ov + np.clip(dd, -cv, cv))  # (inside, old + (value - old) is the value)
+    dvalue = np.where(v_through, vc * (-2 * (ret - value_pred)) / dtype(B), 0).astype(dtype)
     dz2p = (dlogits @ w["wa"]) * (1 - h2p * h2p)
     dz1p = (dz2p @ w["w2p"]) * (1 - h1p * h1p)
     dz2v = (dvalue[:, None] * w["wv"]) * (1 - h2v * h2v)
     dz1v = (dz2v @ w["w2v"]) * (1 - h1v * h1v)
     return dict(x=x, h1p=h1p, h2p=h2p, h1v=h1v, h2v=h2v, dz1p=dz1p, dz2p=dz2p, dlogits=dlogits, dz1v=dz1v, dz2v=dz2v,
-                dvalue=dvalue, t_policy=-np.minimum(p1, p2), t_value=(ret - value) ** 2, t_entropy=-entropy, ratio=ratio,
-                log_ratio=log_ratio, clipped=(np.abs(ratio - 1) > c).astype(dtype), p=p, lsm=lsm, adv=adv)
+                dvalue=dvalue, t_policy=-np.minimum(p1, p2), t_value=(ret - value_pred) ** 2, t_entropy=-entropy, ratio=ratio,
+                log_ratio=log_ratio, clipped=(np.abs(ratio - 1) > c).astype(dtype), p=p, lsm=lsm, adv=adv, value=value,
+                v_through=v_through)
 
 
 # state-dict key of a layer's weight -> (its pre-activation derivative, its input) in ppo_terms
@@ -185,14 +207,14 @@ PPO_LAYERS = {
 
 
 def ppo_reference(state_dict, obs_int8, actions, old_log_probs, advantages, returns, clip_range, ent_coef, vf_coef,
-                  normalize, dtype=np.float64):
-    """SB3's PPO.train loss of one minibatch (defaults, clip_range_vf = None) and its gradient, derived by
+                  normalize, dtype=np.float64, clip_range_vf=None, old_values=None):
+    """SB3's PPO.train loss of one minibatch (clip_range_vf with old_values [B]: value clipping) and its gradient, derived by
     hand, in numpy at precision dtype: obs_int8 [B, D], actions, old_log_probs, advantages, returns [B].
     Returns (grads {state-dict key: array in nn.Linear layout}, stats [8]: STAT_NAMES then two zeros).  The
     min passes the advantage where its unclipped branch is the smaller or the ratio lies inside the clip
     interval, which is autograd's result off the clip edges."""
     t = ppo_terms(state_dict, obs_int8, actions, old_log_probs, advantages, returns, clip_range, ent_coef, vf_coef,
-                  normalize, dtype)
+                  normalize, dtype, clip_range_vf, old_values)
     grads = {}
     for layer, (dz, inp) in PPO_LAYERS.items():
         d = t[dz] if t[dz].ndim == 2 else t[dz][:, None]
@@ -260,6 +282,38 @@ class MlpPolicyReference(nn.Module):
         logits = self.action_net(self.mlp_extractor.policy_net(obs_float))
         value = self.value_net(self.mlp_extractor.value_net(obs_float))
         return logits, value[:, 0]
+
+
+def check_target_kl(target_kl):
+    """target_kl as a float, or None; ValueError for a negative or non-finite one."""
+    if target_kl is None:
+        return None
+    k = float(target_kl)
+    if not (math.isfinite(k) and k >= 0.0):
+        raise ValueError("target_kl must be finite and at least 0 (None: no early stop)")
+    return k
+
+
+def _ppo_extra(device, stop_at=None, ordinal=0, clip_range_vf=None, old_values=None, target_kl=None):
+    """The PgtgPpoExtra of a gated or value-clipped call (include/pgtg.h), or None where nothing is asked for."""
+    if stop_at is None and clip_range_vf is None and target_kl is None:
+        return None
+    x = _abi.PgtgPpoExtra()
+    if stop_at is not None:
+        if stop_at.dtype != torch.int32 or stop_at.numel() != 1 or stop_at.device != device:
+            raise ValueError(f"stop_at: an int32 tensor of one word on {device}")
+        if int(ordinal) < 1:
+            raise ValueError("ordinal counts from 1 where stop_at is given")
+        x.stop_at, x.ordinal = stop_at.data_ptr(), int(ordinal)
+    if clip_range_vf is not None:
+        x.flags |= _abi.PGTG_PPO_CLIP_VF
+        x.clip_range_vf, x.old_values = clip_range_vf, old_values.data_ptr()
+    if target_kl is not None:
+        if stop_at is None:
+            raise ValueError("target_kl needs stop_at")
+        x.flags |= _abi.PGTG_PPO_TARGET_KL
+        x.target_kl = target_kl
+    return x
 
 
 class DevicePolicy:
@@ -359,7 +413,8 @@ class DevicePolicy:
         return out
 
     def ppo_grad(self, rollout, indices, grads=None, clip_range: float = 0.2, ent_coef: float = 0.0,
-                 vf_coef: float = 0.5, normalize_advantage: bool = True, adv_stats=None):
+                 vf_coef: float = 0.5, normalize_advantage: bool = True, adv_stats=None, clip_range_vf=None,
+                 stats_out=None, target_kl=None, stop_at=None, ordinal: int = 0):
         """One PPO minibatch on the samples `indices` (int64 [B] device tensor of flat sample indices,
         rollout.sample_index's order; repeats allowed) of a finished int8 rollout: SB3's loss and its gradient
         with respect to the twelve tensors, by pgtg_ppo_grad (three launches; the [B, D] batch is never
@@ -371,9 +426,17 @@ class DevicePolicy:
         the std of the advantages it stands as an advantage of 0, so that no mask has to reach the host.
         adv_stats: a float32 [2] device tensor {mean, 1 / (std + 1e-8)} (self.adv_stats) to normalise with in
         place of the torch reductions; the call then launches no torch kernel (the stats tensor is allocated
-        without a fill: k_ppo_reduce writes all eight)."""
+        without a fill: k_ppo_reduce writes all eight).
+        clip_range_vf: SB3's value clipping against rollout.values (None: none, today's bits).  stats_out: a
+        contiguous float32 [8] device tensor (a row of an update's [M, 8] buffer) to write the statistics into
+        in place of a fresh tensor.  stop_at (int32 device word) with ordinal m = 1, 2, ...: the gate of an
+        update with target_kl (include/pgtg.h PgtgPpoExtra): the launches do nothing once stop_at holds a value
+        below m, and with target_kl given this minibatch stores stop_at = m when its approx_kl exceeds
+        1.5 * target_kl and nothing has stopped the update yet.  ValueError for a negative or non-finite
+        clip_range_vf or target_kl, with nothing launched."""
         if not self._loaded:
             raise ValueError("load_state_dict() first")
+        clip_range_vf, target_kl = check_clip_range_vf(clip_range_vf), check_target_kl(target_kl)
         ro = rollout
         if ro.env is not self.env or ro.obs_dim != self.obs_dim:
             raise ValueError("the rollout is of another env or obs_dim")
@@ -397,7 +460,10 @@ class DevicePolicy:
             setattr(raw, field, g.data_ptr())
         if adv_stats is not None:
             adv_stats = self._out(adv_stats, 2, torch.float32, "adv_stats")
-        if adv_stats is not None and B > 0:
+        extra = _ppo_extra(self.device, stop_at, ordinal, clip_range_vf, ro.values, target_kl)
+        if stats_out is not None:
+            stats = self._out(stats_out, 8, torch.float32, "stats_out")
+        elif adv_stats is not None and B > 0:
             stats = torch.empty(8, dtype=torch.float32, device=self.device)
         else:
             stats = torch.zeros(8, dtype=torch.float32, device=self.device)
@@ -421,18 +487,21 @@ class DevicePolicy:
                              advantages=p(ro.advantages), returns=p(ro.returns), packed=p(self._packed),
                              adv_stats=p(adv_stats), clip_range=float(clip_range), ent_coef=float(ent_coef),
                              vf_coef=float(vf_coef), workspace=p(ws), grads=raw, stats=p(stats))
-        self._ppo_keep = (idx, adv_stats, stats, grads)
+        self._ppo_keep = (idx, adv_stats, stats, grads, stop_at)
         self.env._bind_stream()
-        rc = self.env._lib.pgtg_ppo_grad(self.env._h, C.byref(a))
+        if extra is None:
+            rc = self.env._lib.pgtg_ppo_grad(self.env._h, C.byref(a))
+        else:
+            rc = self.env._lib.pgtg_ppo_grad_ex(self.env._h, C.byref(a), C.byref(extra))
         if rc != _abi.PGTG_OK:
             self._fail(rc)
         return grads, stats
 
-    def adv_stats(self, rollout, indices, out=None):
+    def adv_stats(self, rollout, indices, out=None, stop_at=None, ordinal: int = 0):
         """{mean, 1 / (std + 1e-8)} of the advantages of the samples `indices` (as ppo_grad takes them; at least
         two) into out or a fresh float32 [2] device tensor: one launch of k_ppo_adv_stats on the env's stream
         (include/pgtg.h pgtg_ppo_adv_stats), for ppo_grad's adv_stats.  The unbiased std; an index outside the
-        rollout stands as an advantage of 0, as in ppo_grad's own reductions."""
+        rollout stands as an advantage of 0, as in ppo_grad's own reductions.  stop_at, ordinal: ppo_grad's gate."""
         ro = rollout
         if ro.env is not self.env:
             raise ValueError("the rollout is of another env")
@@ -442,10 +511,15 @@ class DevicePolicy:
         if idx.numel() < 2:
             raise ValueError("adv_stats needs at least two samples (SB3 does not normalise a batch of one)")
         out = self._out(out, 2, torch.float32, "out")
-        self._adv_keep = (idx, out)
+        extra = _ppo_extra(self.device, stop_at, ordinal)
+        self._adv_keep = (idx, out, stop_at)
         self.env._bind_stream()
-        rc = self.env._lib.pgtg_ppo_adv_stats(self.env._h, C.c_void_p(ro.advantages.data_ptr()), C.c_void_p(idx.data_ptr()),
-                                              idx.numel(), ro.n_steps, ro.num_envs, C.c_void_p(out.data_ptr()))
+        args = (self.env._h, C.c_void_p(ro.advantages.data_ptr()), C.c_void_p(idx.data_ptr()), idx.numel(), ro.n_steps,
+                ro.num_envs, C.c_void_p(out.data_ptr()))
+        if extra is None:
+            rc = self.env._lib.pgtg_ppo_adv_stats(*args)
+        else:
+            rc = self.env._lib.pgtg_ppo_adv_stats_ex(*args, C.byref(extra))
         if rc != _abi.PGTG_OK:
             self._fail(rc)
         return out
@@ -492,10 +566,12 @@ class DeviceAdam:
             setattr(self._raw.exp_avg, field, self.exp_avg[key].data_ptr())
             setattr(self._raw.exp_avg_sq, field, self.exp_avg_sq[key].data_ptr())
 
-    def step(self, grads=None, max_grad_norm: float | None = 0.5) -> None:
+    def step(self, grads=None, max_grad_norm: float | None = 0.5, stop_at=None, ordinal: int = 0) -> None:
         """One optimiser step from grads {state-dict key: contiguous float32 device tensor} (default: the
         module's .grad tensors; they are read, not written): the global norm over all twelve, the clip to
-        max_grad_norm (None or inf: none), Adam, and the policy's packed buffer rewritten."""
+        max_grad_norm (None or inf: none), Adam, and the policy's packed buffer rewritten.  stop_at, ordinal:
+        ppo_grad's gate; the step of ordinal m does nothing once stop_at holds a value up to m.  step_count
+        counts the call either way: Rollout.update sets it right after its one read of stop_at."""
         pol, shapes = self.policy, weight_shapes(self.policy.obs_dim)
         raw = self._raw
         for field, (key, _) in WEIGHT_KEYS.items():
@@ -510,9 +586,13 @@ class DeviceAdam:
         raw.step = self.step_count + 1
         raw.lr, (raw.beta1, raw.beta2), raw.eps = float(self.lr), self.betas, self.eps
         raw.max_grad_norm = math.inf if max_grad_norm is None else float(max_grad_norm)
-        self._keep = grads
+        extra = _ppo_extra(pol.device, stop_at, ordinal)
+        self._keep = (grads, stop_at)
         pol.env._bind_stream()
-        rc = pol.env._lib.pgtg_ppo_step(pol.env._h, C.byref(raw))
+        if extra is None:
+            rc = pol.env._lib.pgtg_ppo_step(pol.env._h, C.byref(raw))
+        else:
+            rc = pol.env._lib.pgtg_ppo_step_ex(pol.env._h, C.byref(raw), C.byref(extra))
         if rc != _abi.PGTG_OK:
             pol._fail(rc)
         self.step_count += 1

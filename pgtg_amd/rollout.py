@@ -24,6 +24,7 @@ which reads obs[t] and writes the action, value and log-probability rows) the lo
     ro.collect(policy)                                           # T x (k_policy, the tick, V(terminal_obs)), k_gae
     ro.update(policy, module, optimizer)                         # SB3's PPO.train: per minibatch k_ppo_loss, k_ppo_dw1,
                                                                  # k_ppo_reduce into module's .grad, then clip, step, repack
+    ro.train_log()                                               # its train/ log (k_ppo_expl_var, k_ppo_log)
 
 While a Rollout records, it owns the handle's flat bindings (set_flat_outputs / set_flat_scalars): bind
 nothing else to them until `close()`.
@@ -69,6 +70,58 @@ def gae_reference(rewards, values, dones, truncated_only, terminal_values, last_
         last_gae_lam = delta + gamma * gae_lambda * next_non_terminal * last_gae_lam
         advantages[step] = last_gae_lam
     return advantages, advantages + values
+
+
+PERM_ROUNDS = 6     # Feistel rounds of k_ppo_perm (pgtg_ppo_log.h kPermRounds)
+PERM_WALK_CAP = 64  # cycle-walk steps of an element at most (kPermWalkCap)
+
+
+def permutation_reference(total: int, seed: int, counter: int, return_walk: bool = False):
+    """The permutation of [0, total) k_ppo_perm writes for (seed, counter), int64 [total], restated in numpy,
+    bit-equal with the kernel: an alternating Feistel network over bits = ceil(log2 total) bits (the low
+    bits // 2 and the high bits - bits // 2 take turns being xored with the round function of the other:
+    policy_uniform's splitmix64 finaliser of (seed, counter, round, half) in a domain of its own), walked until
+    the value falls below total.  Every element is computed on its own.  return_walk: also the longest walk."""
+    import numpy as np
+    total = int(total)
+    if total < 1:
+        raise ValueError("total must be at least 1")
+    M = (1 << 64) - 1
+    bits = (total - 1).bit_length()
+    a, b = bits // 2, bits - bits // 2
+    mask_a, mask_b = np.uint64((1 << a) - 1), np.uint64((1 << b) - 1)
+    key = np.uint64((int(seed) & M) ^ ((int(counter) * 0x9E3779B97F4A7C15) & M) ^ 0x70706F5F7065726D)
+
+    def f(half, rnd):
+        with np.errstate(over="ignore"):
+            z = key ^ (half * np.uint64(0xD1B54A32D192ED03)) ^ np.uint64(((rnd + 1) * 0xA0761D6478BD642F) & M)
+            z = z + np.uint64(0x9E3779B97F4A7C15)
+            z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+            z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+            return z ^ (z >> np.uint64(31))
+
+    def feistel(x):
+        lo, hi = x & mask_a, x >> np.uint64(a)
+        for rnd in range(PERM_ROUNDS):
+            if rnd & 1:
+                hi = hi ^ (f(lo, rnd) & mask_b)
+            else:
+                lo = lo ^ (f(hi, rnd) & mask_a)
+        return (hi << np.uint64(a)) | lo
+
+    x = feistel(np.arange(total, dtype=np.uint64))
+    walk = 1
+    while True:
+        out = x >= np.uint64(total)
+        if not out.any():
+            break
+        if walk >= PERM_WALK_CAP:  # (the kernel flags these elements and writes their own index)
+            x[out] = np.nonzero(out)[0].astype(np.uint64)
+            break
+        x[out] = feistel(x[out])
+        walk += 1
+    perm = x.astype(np.int64)
+    return (perm, walk) if return_walk else perm
 
 
 class Rollout:
@@ -124,6 +177,11 @@ class Rollout:
         self._finished = False
         self._last_values = None
         self._last_buf = None  # collect()'s V(obs[T])
+        self.n_updates = 0      # epochs counted by every update() so far: SB3's _n_updates
+        self._updates = 0       # update() calls so far: the counter of perm_seed's permutations
+        self._train = None      # the last update's statistics buffer, shape and log
+        self._stop_word = None  # target_kl's device word
+        self._ev_ws = None      # k_ppo_expl_var's workspace
 
     @property
     def nbytes(self) -> int:
@@ -274,55 +332,188 @@ class Rollout:
                    self.log_probs[t, e], self.advantages[t, e], self.returns[t, e])
 
     # -- the PPO update ---------------------------------------------------------------------------
+    def _call(self, rc: int) -> None:
+        if rc != _abi.PGTG_OK:
+            from .vector import _check
+            _check(rc, self.env._h)
+
+    def permutation(self, seed: int, counter: int, out=None):
+        """The permutation of [0, T * N) of (seed, counter) as an int64 device tensor: one launch of k_ppo_perm
+        (include/pgtg.h pgtg_ppo_perm; permutation_reference restates it), no torch kernel."""
+        import torch
+        total = self.n_steps * self.num_envs
+        if out is None:
+            out = torch.empty(total, dtype=torch.int64, device=self.device)
+        m = (1 << 64) - 1
+        self.env._bind_stream()
+        self._call(self.env._lib.pgtg_ppo_perm(self.env._h, total, int(seed) & m, int(counter) & m,
+                                               C.c_void_p(out.data_ptr())))
+        return out
+
+    def explained_variance(self, out=None):
+        """{1 - r, r}, r = var(returns - values) / var(returns), of the finished rollout as a float32 [2] device
+        tensor: SB3's explained_variance and the ratio it is one minus (three launches of k_ppo_expl_var,
+        include/pgtg.h pgtg_ppo_expl_var; nothing synchronises)."""
+        import torch
+        if not self._finished:
+            raise ValueError("the rollout is not finished: collect() or finish() first")
+        if self._ev_ws is None:
+            nbytes = C.c_uint64()
+            self._call(self.env._lib.pgtg_ppo_expl_var_workspace_bytes(C.byref(nbytes)))
+            self._ev_ws = torch.empty(nbytes.value // 8, dtype=torch.float64, device=self.device)
+        if out is None:
+            out = torch.empty(2, dtype=torch.float32, device=self.device)
+        p = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
+        self.env._bind_stream()
+        self._call(self.env._lib.pgtg_ppo_expl_var(self.env._h, p(self.values), p(self.returns),
+                                                   self.n_steps * self.num_envs, p(self._ev_ws), p(out)))
+        return out
+
+    def _read_log(self) -> dict:
+        """Launch the explained variance and k_ppo_log over the last update's statistics, read the struct back
+        (the one host synchronisation) and keep the dict."""
+        import torch
+        st = self._train
+        ev = self.explained_variance()
+        raw = torch.empty(C.sizeof(_abi.PgtgPpoLog), dtype=torch.uint8, device=self.device)
+        p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+        self.env._bind_stream()
+        self._call(self.env._lib.pgtg_ppo_log(self.env._h, p(st["stats"]), st["M"], st["per_epoch"], p(st["stop"]), p(ev),
+                                              p(raw)))
+        log = _abi.PgtgPpoLog.from_buffer_copy(raw.cpu().numpy().tobytes())
+        st["log"] = dict(entropy_loss=log.entropy_loss, policy_gradient_loss=log.policy_gradient_loss,
+                         value_loss=log.value_loss, approx_kl=log.approx_kl, clip_fraction=log.clip_fraction,
+                         loss=log.loss, explained_variance=log.explained_variance, n_updates=None,
+                         early_stop=bool(log.early_stop), minibatches=int(log.minibatches), epochs=int(log.epochs),
+                         variance_ratio=log.variance_ratio)
+        return st["log"]
+
+    def train_log(self) -> dict:
+        """SB3's train/ log of the last update(): entropy_loss, policy_gradient_loss, value_loss and
+        clip_fraction (means over the minibatches run), approx_kl (mean over the last run epoch), loss (the last
+        run minibatch's), explained_variance (of the rollout's values against its returns, as they stand now),
+        n_updates (the epochs counted by every update() of this rollout so far, SB3's _n_updates), early_stop
+        and minibatches (target_kl), plus epochs and variance_ratio (1 - explained_variance before its
+        rounding).  Reduced on the device (k_ppo_expl_var, k_ppo_log: four launches); this call synchronises
+        the host, once; after an update with target_kl it returns what that update already read."""
+        st = self._train
+        if st is None:
+            raise RuntimeError("update() first")
+        if st["M"] == 0:
+            nan = float("nan")
+            log = dict(entropy_loss=nan, policy_gradient_loss=nan, value_loss=nan, approx_kl=nan, clip_fraction=nan,
+                       loss=nan, explained_variance=nan, early_stop=False, minibatches=0, epochs=0, variance_ratio=nan)
+        else:
+            log = dict(st["log"] if st["log"] is not None else self._read_log())
+        log["n_updates"] = self.n_updates
+        return log
+
     def update(self, policy, module, optimizer, n_epochs: int = 10, batch_size: int = 64, clip_range: float = 0.2,
                ent_coef: float = 0.0, vf_coef: float = 0.5, max_grad_norm: float = 0.5,
-               normalize_advantage: bool = True, generator=None) -> list:
+               normalize_advantage: bool = True, generator=None, clip_range_vf=None, target_kl=None,
+               perm_seed=None) -> list:
         """SB3's PPO.train loop over the finished rollout with the library's gradient: per epoch one
         torch.randperm(T * N) on the device (from `generator` if given), per minibatch of batch_size samples
         policy.ppo_grad (k_ppo_loss, k_ppo_dw1, k_ppo_reduce on the int8 rows) straight into the .grad tensors
         of `module` (an MlpPolicyReference on the env's device whose weights `policy` holds), then torch's
         clip_grad_norm_, optimizer.step() and policy.load_state_dict(module.state_dict()).  Returns the
-        per-minibatch stats tensors (policy.STAT_NAMES), still on the device; nothing synchronises.
+        per-minibatch stats tensors (policy.STAT_NAMES), still on the device (rows of one [M, 8] buffer);
+        nothing synchronises.
         With a policy.DeviceAdam over (policy, module) as the optimizer a minibatch is this library's launches
         alone: policy.adv_stats (k_ppo_adv_stats; when normalising more than one sample), policy.ppo_grad with
         those statistics, and optimizer.step(max_grad_norm=...) (k_ppo_gnorm, k_ppo_adam: clip, Adam and the
-        repack) -- no torch kernel but the epoch's randperm, no clip_grad_norm_ and no load_state_dict."""
+        repack) -- no clip_grad_norm_ and no load_state_dict.
+        clip_range_vf: SB3's value-function clipping against the rollout's values (None: none).
+        perm_seed: None keeps torch.randperm and `generator`; an int draws epoch k of this rollout's u-th update
+        (u = 0, 1, ...) as permutation(perm_seed, u * n_epochs + k) by k_ppo_perm, a function of those numbers
+        alone on any build, and then a DeviceAdam update launches no torch kernel at all.
+        target_kl: SB3's early stop, approx_kl > 1.5 * target_kl before a minibatch's optimiser step ends the
+        update.  With a DeviceAdam nothing synchronises per minibatch: a device word stop_at (zeroed on the
+        stream as the update starts) is set by the stopping minibatch's own k_ppo_reduce, every later launch
+        returns at its gate, and the host reads the word once, at the end, with the log (train_log() then costs
+        nothing more): the one synchronisation of the update.  optimizer.step_count is set from that read, and
+        the returned list is cut to the minibatches run.  With a torch.optim optimizer, approx_kl is read on the
+        host per minibatch and the loop breaks, as SB3's does.
+        ValueError for a negative or non-finite clip_range_vf or target_kl, with nothing launched."""
         import torch
-        from .policy import DeviceAdam
+        from .policy import DeviceAdam, check_clip_range_vf, check_target_kl
         if not self._finished:
             raise ValueError("the rollout is not finished: collect() or finish() first")
         if int(batch_size) < 1 or int(n_epochs) < 0:
             raise ValueError("batch_size must be at least 1 and n_epochs at least 0")
+        clip_range_vf, target_kl = check_clip_range_vf(clip_range_vf), check_target_kl(target_kl)
         params = dict(module.named_parameters())
         grads = {}
         for key, p in params.items():
             if p.grad is None:
                 p.grad = torch.zeros_like(p)
             grads[key] = p.grad
-        total, out = self.n_steps * self.num_envs, []
-        if isinstance(optimizer, DeviceAdam):
-            if optimizer.policy is not policy or optimizer.module is not module:
-                raise ValueError("the DeviceAdam was built over another policy or module")
-            for _ in range(int(n_epochs)):
-                perm = torch.randperm(total, device=self.device, generator=generator)
-                for lo in range(0, total, int(batch_size)):
-                    idx = perm[lo:lo + int(batch_size)]
-                    st = policy.adv_stats(self, idx) if normalize_advantage and idx.numel() > 1 else None
-                    _, stats = policy.ppo_grad(self, idx, grads=grads, clip_range=clip_range, ent_coef=ent_coef,
-                                               vf_coef=vf_coef, normalize_advantage=normalize_advantage, adv_stats=st)
-                    optimizer.step(grads=grads, max_grad_norm=max_grad_norm)
-                    out.append(stats)
-            return out
-        for _ in range(int(n_epochs)):
-            perm = torch.randperm(total, device=self.device, generator=generator)
-            for lo in range(0, total, int(batch_size)):
-                _, stats = policy.ppo_grad(self, perm[lo:lo + int(batch_size)], grads=grads, clip_range=clip_range,
-                                           ent_coef=ent_coef, vf_coef=vf_coef, normalize_advantage=normalize_advantage)
+        n_epochs, bs = int(n_epochs), int(batch_size)
+        total = self.n_steps * self.num_envs
+        per_epoch = (total + bs - 1) // bs
+        M = n_epochs * per_epoch
+        device_adam = isinstance(optimizer, DeviceAdam)
+        if device_adam and (optimizer.policy is not policy or optimizer.module is not module):
+            raise ValueError("the DeviceAdam was built over another policy or module")
+        stats = torch.empty((max(M, 1), 8), dtype=torch.float32, device=self.device)
+        stop = None
+        if target_kl is not None:
+            if self._stop_word is None:
+                self._stop_word = torch.zeros(1, dtype=torch.int32, device=self.device)
+            stop = self._stop_word
+            stop.zero_()
+        self._train = dict(stats=stats, M=M, per_epoch=per_epoch, stop=stop, log=None)
+        u = self._updates
+        self._updates += 1
+
+        def epoch_perm(k):
+            if perm_seed is None:
+                return torch.randperm(total, device=self.device, generator=generator)
+            return self.permutation(perm_seed, u * n_epochs + k)
+
+        common = dict(grads=grads, clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef,
+                      normalize_advantage=normalize_advantage, clip_range_vf=clip_range_vf)
+        run = M
+        if device_adam:
+            count_before = optimizer.step_count
+            gate = {} if stop is None else dict(stop_at=stop)
+            m = 0
+            for k in range(n_epochs):
+                perm = epoch_perm(k)
+                for lo in range(0, total, bs):
+                    m += 1
+                    if stop is not None:
+                        gate["ordinal"] = m
+                    idx = perm[lo:lo + bs]
+                    st = policy.adv_stats(self, idx, **gate) if normalize_advantage and idx.numel() > 1 else None
+                    policy.ppo_grad(self, idx, adv_stats=st, stats_out=stats[m - 1], target_kl=target_kl, **gate, **common)
+                    optimizer.step(grads=grads, max_grad_norm=max_grad_norm, **gate)
+            if stop is not None and M:
+                log = self._read_log()  # (the one synchronisation: stop_at and the log together)
+                run = log["minibatches"]
+                optimizer.step_count = count_before + (run - 1 if log["early_stop"] else M)
+                self.n_updates += log["epochs"]
+            else:
+                self.n_updates += n_epochs
+            return [stats[i] for i in range(run)]
+        m, stopped = 0, False
+        for k in range(n_epochs):
+            perm = epoch_perm(k)
+            for lo in range(0, total, bs):
+                m += 1
+                policy.ppo_grad(self, perm[lo:lo + bs], stats_out=stats[m - 1], **common)
+                if target_kl is not None and bool(stats[m - 1, 4] > 1.5 * target_kl):  # (a host read, as SB3's)
+                    stopped = True
+                    break
                 torch.nn.utils.clip_grad_norm_(params.values(), max_grad_norm)
                 optimizer.step()
                 policy.load_state_dict(module.state_dict())
-                out.append(stats)
-        return out
+            self.n_updates += 1
+            if stopped:
+                stop.fill_(m)  # (k_ppo_log reads the word)
+                run = m
+                break
+        return [stats[i] for i in range(run)]
 
     def close(self) -> None:
         """Unbind the flat rows and scalars from the handle (the tensors stay valid)."""
