@@ -627,6 +627,17 @@ int pgtg_get_queue_maps(pgtg_handle* h, uint64_t* maps);
 /* Step-kernel launches since create: one per pgtg_step, and per pgtg_step_many one per tick or, where it runs
  * several ticks in a launch, one per such launch.  Host counter, no synchronisation. */
 int pgtg_get_step_launches(pgtg_handle* h, uint64_t* launches);
+/* Tuning and testing, beside PgtgConfig.tune_queue_grid: the block shares of the multi-tick step launches of a
+ * k_envq handle.  Workgroup w of the queue grid owns counts[w] consecutive blocks (of envs-per-workgroup envs
+ * each), workgroup 0 from block 0 on.  By default every such launch of two ticks or more re-derives the counts
+ * on the device from the workgroups' measured time per block; results never depend on them.
+ * pgtg_set_block_shares: counts == NULL keeps the table; otherwise n must be the queue grid, the counts must sum
+ * to the handle's blocks and none may exceed what a workgroup's request list holds (three times the equal
+ * share, rounded up), else PGTG_E_INVALID.  freeze != 0 stops the device from updating them, 0 resumes it.
+ * pgtg_get_block_shares: the queue grid into *grid (if not NULL) and, if counts is not NULL, the current counts
+ * (n must be the queue grid).  Both synchronise. */
+int pgtg_set_block_shares(pgtg_handle* h, const uint32_t* counts, uint32_t n, int32_t freeze);
+int pgtg_get_block_shares(pgtg_handle* h, uint32_t* counts, uint32_t n, uint32_t* grid);
 /* Map-queue refill requests served from the overflow lists since create (step launches of one round
  * of workgroups list at most 64 requests per workgroup; the rest go to lists shared by residue mod 8
  * and are served by other workgroups' helper waves in the next launch).  Synchronises. */

@@ -13,7 +13,7 @@ DEPS = [SRC, os.path.join(PKG, "csrc", "pgtg_device.h"), os.path.join(PKG, "csrc
         os.path.join(PKG, "csrc", "pgtg_snapshot.h"),
         os.path.join(PKG, "csrc", "pgtg_rollout.h"), os.path.join(PKG, "csrc", "pgtg_policy.h"),
         os.path.join(PKG, "csrc", "pgtg_ppo.h"), os.path.join(PKG, "csrc", "pgtg_ppo_step.h"),
-        os.path.join(PKG, "csrc", "pgtg_ppo_log.h"),
+        os.path.join(PKG, "csrc", "pgtg_ppo_log.h"), os.path.join(PKG, "csrc", "pgtg_shares.h"),
         os.path.join(os.path.dirname(PKG), "include", "pgtg.h")]
 OUT = os.path.join(PKG, "libpgtg_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -34,6 +34,8 @@
 #include "pgtg_ppo_step.h"
 #include "pgtg_ppo_log.h"
 #include "pgtg_snapshot.h"
+#define PGTG_SHARE_FN __host__ __device__ inline
+#include "pgtg_shares.h"
 
 namespace pgtg {
 namespace dv {
@@ -2808,7 +2810,15 @@ constexpr int kMaxQueueGrid = 4096;  // k_envq's persistent grid at most
 // overflow lists' lengths
 constexpr int kQctrBlocks = 2 * kMaxQueueGrid;
 constexpr int kQctrOvfLen = kQctrBlocks + 3;
-constexpr int kQctrWords = kQctrOvfLen + 24;
+constexpr int kQctrWords = kQctrOvfLen + 24;  // (what a reset of the lists clears)
+// behind them in the same allocation, so that the step kernels' parameter lists stay as they were: k_envq<BIG, true>'s
+// share table (own_start[grid], own_count[grid]) and its words per workgroup (kWgWords 64-bit words each)
+constexpr int kQctrOwn = (kQctrWords + 1) & ~1;
+constexpr int kQctrWg = kQctrOwn + 2 * kMaxQueueGrid;
+// k_envq<BIG, true>'s words per workgroup: wall clock at the launch's start, at the end of its last tick,
+// and the length of the list its drain served (0 once k_drained has counted it)
+constexpr int kWgWords = 3;
+constexpr int kQctrAlloc = kQctrWg + 2 * kWgWords * kMaxQueueGrid;
 __device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) x += (uint32_t)__shfl_xor((int)x, o);
@@ -3414,7 +3424,8 @@ __device__ __forceinline__ void sub_barrier(uint32_t* ctr, uint32_t target) {
 // (One shared request list instead: 497 vs 456 us per 1 048 576-env launch, its counter a hot spot on
 // every env wave's path; static blocks blockIdx.x + k * gridDim.x: 455 us against the counter's 424.)
 // FUSED (pgtg_step_many): `ticks` ticks in one launch, tick k reading its actions at actions + k *
-// act_stride.  Workgroup w owns blocks w, w + gridDim.x, ... for the whole launch and steps them all for
+// act_stride.  Workgroup w owns the blocks own_start[w] .. + own_count[w] (the share table) for the
+// whole launch and steps them all for
 // one tick, then for the next: no block counter, and nothing passes between workgroups -- an env's
 // record, ring, qstate byte and outputs, and a workgroup's request lists, are written and read by waves
 // of that one workgroup -- so no workgroup waits for another, and a slow one is waited for once per
@@ -3424,7 +3435,8 @@ __device__ __forceinline__ void sub_barrier(uint32_t* ctr, uint32_t target) {
 // workgroup reads any of it before the launch ends.  Progress: the helper serving tick t waits only for
 // the env and writer waves' arrivals at the end of tick t - 1; those waves, in tick t, wait only for the
 // helper's fills of tick t - 1, which waited for tick t - 2: every wait is for a strictly earlier tick.
-// The launch before must have left request lists of the same ownership (pgtg_handle::q_static), since an
+// The launch before must have left the request lists empty (pgtg_handle::q_static; a multi-tick launch does:
+// its helper's last pass, the drain, serves the last tick's list), since an
 // entry the helper makes in the first tick may be taken in the second.  The results are those of
 // `ticks` launches; every tick makes every store a launch of its own would make.
 // The map-queue step's observation images.  With <= 32 envs per workgroup they all sit in wave 0
@@ -3523,6 +3535,18 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
   const DevCfg& c = *cfg;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const uint64_t t_start = stagger_start(L, S);
+  // FUSED: the workgroup's blocks, a contiguous range from the share table (own_start[grid], own_count[grid];
+  // DESIGN 5r), and its words wgw[grid][kWgWords]: its wall clock at the launch's start and at its last tick's end
+  // (k_shares reads the pair behind the launch) and the requests its drain served (k_drained counts them)
+  // The ranges are over the blocks in the order (w, k) -> block w + k * gridDim.x, column after column (`phys`
+  // below): with equal shares a workgroup owns exactly blocks blockIdx.x + k * gridDim.x, as before the table, and
+  // with any shares the workgroups' k-th blocks lie side by side in memory.  (Ranges over the plain block index
+  // measured 8 % slower at equal shares: every workgroup streaming through a region of its own.)
+  const uint32_t* own_tab = S.qctr + kQctrOwn;
+  unsigned long long* wgw = reinterpret_cast<unsigned long long*>(S.qctr + kQctrWg);
+  const uint64_t b0 = FUSED ? (uint64_t)__builtin_amdgcn_readfirstlane((int)own_tab[blockIdx.x]) : (uint64_t)blockIdx.x;
+  const uint32_t bc = FUSED ? (uint32_t)__builtin_amdgcn_readfirstlane((int)own_tab[gridDim.x + blockIdx.x]) : 1u;
+  if (FUSED && tid == 0) wgw[kWgWords * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
   STAMP(0);  // (the env waves' is each block's start)
   STAMPR(2);  // (wall clock: every wave's start and end, slots 2 and 3 -- the launch's ramp and tail)
   const int env_waves = (L.envs + 63) / 64, gen_wave = env_waves;
@@ -3533,6 +3557,24 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
   uint32_t par = (qsel >> 2) & 1u;
   const uint64_t nblk = (S.n + (uint64_t)L.envs - 1) / (uint64_t)L.envs;
   const uint64_t cap = queue_req_cap(nblk, gridDim.x, L.envs);  // requests per workgroup and launch
+  // FUSED: the block at place j of the column order -- columns 0 .. p_full - 1 hold p_rows blocks, the others one fewer
+  // (more blocks than workgroups: p_rows >= 2)
+  const uint32_t p_rows = (uint32_t)((nblk + gridDim.x - 1) / gridDim.x);
+  const uint32_t p_full = nblk % gridDim.x ? (uint32_t)(nblk % gridDim.x) : gridDim.x;
+  const auto phys = [&](uint64_t j) -> uint64_t {
+    if (!FUSED) return j;
+    const uint32_t jj = (uint32_t)j, split = p_full * p_rows;
+    uint32_t w, k;
+    if (jj < split) {
+      w = jj / p_rows;
+      k = jj - w * p_rows;
+    } else {
+      w = (jj - split) / (p_rows - 1u);
+      k = (jj - split) - w * (p_rows - 1u);
+      w += p_full;
+    }
+    return (uint64_t)k * gridDim.x + w;
+  };
   uint2* req_new = S.qreq + ((uint64_t)par * gridDim.x + blockIdx.x) * cap;
   const uint2* req_old = S.qreq + ((uint64_t)(par ^ 1u) * gridDim.x + blockIdx.x) * cap;
   // One round of blocks (every workgroup one block): a helper's time is on the launch's path, so a
@@ -3552,7 +3594,7 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
   if (blockIdx.x == 0 && tid < 8) S.qctr[kQctrOvfLen + ((set_new + 1u) % 3u) * 8u + tid] = 0u;  // (the launch after next's)
   // the first block's qstate bytes, issued before the tables are staged (a later block's: one block ahead)
   uint32_t qs_nx = 0;
-  if (tid < L.envs && (uint64_t)blockIdx.x * L.envs + tid < S.n) qs_nx = S.qstate[(uint64_t)blockIdx.x * L.envs + tid];
+  if (tid < L.envs && bc > 0 && phys(b0) * L.envs + tid < S.n) qs_nx = S.qstate[phys(b0) * L.envs + tid];
   const int pdw = L.plan_stride_dw;
   stage_tables(gtab, false);  // (the map queue runs without lane channels: no sTX reference here)
   uint32_t* st = lds + L.envs * (pdw + L.scratch_dw + L.traf_dw + L.hist_dw);
@@ -3649,15 +3691,32 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
           }
         }
       }
-      if (lane == 0 && made) atomicAdd(&S.counters[2], (unsigned long long)made);  // maps generated
+      if (lane == 0 && made && !(FUSED && tick == ticks)) atomicAdd(&S.counters[2], (unsigned long long)made);  // maps generated
       if (lane == 0 && ovs) atomicAdd(&S.counters[3], (unsigned long long)ovs);  // overflow requests served
-      if (!FUSED || ++tick == ticks) break;
-      // FUSED: this tick's fills are stored (the env waves of the next tick wait for that before they take a
-      // ring head) ...
+      if (!FUSED) break;
+      // FUSED: a list's count is cleared by the pass that served it (the env waves store it anew when they
+      // next fill that list, behind their wait for this pass).  The pass after the last tick, the drain, serves
+      // that tick's list, so the launch leaves both lists empty and both counts 0: the next launch may give
+      // any block to any workgroup.  The drain's maps are counted apart: it leaves the length of the list it
+      // served (the list itself stays where it is), and k_drained, queued ahead of whatever next serves or drops
+      // request lists, counts the entries a launch per tick would have made there.
+      if (lane == 0 && cnt) S.qctr[(par ^ 1u) * gridDim.x + blockIdx.x] = 0u;
+      if (bc == 0) {  // no block: the list served was one a launch of k_envq<BIG, false> left; the other is stale
+        if (lane == 0) S.qctr[par * gridDim.x + blockIdx.x] = 0u;
+        break;
+      }
+      if (tick == ticks) {
+        if (lane == 0) wgw[kWgWords * blockIdx.x + 2] = made;
+        break;
+      }
+      ++tick;
+      // this tick's fills are stored (the env waves of the next tick wait for that before they take a
+      // ring head; nobody waits for the last tick's) ...
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       if (lane == 0) __hip_atomic_store(fdone, tick, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       // ... then the next list: every env and writer wave has arrived at the end of tick `tick - 1`, with
-      // its requests and their count stored.  The helper waits for nothing later than the tick it serves.
+      // its requests and their count stored.  The helper waits for nothing later than the tick it serves
+      // (the drain: for the last tick's arrivals).
       while (__hip_atomic_load(rdone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < tick * (uint32_t)(kBlock / 64 - 1))
         __builtin_amdgcn_s_sleep(4);
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -3676,15 +3735,16 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
   const int nthr = np * 64;
   uint32_t bar = 0;  // running sub_barrier target
   uint32_t tick = 0;  // (FUSED)
-  for (uint64_t blk = blockIdx.x; blk < nblk;) {
+  const uint64_t bend = FUSED ? b0 + bc : nblk;  // (FUSED: the end of the workgroup's range)
+  for (uint64_t blk = b0; blk < bend;) {
     STAMP(0);
     uint32_t got = 0xffffffffu;
     if (!FUSED && tid == 0 && nblk > gridDim.x && *qn + 2u * (uint32_t)L.envs <= cap) got = atomicAdd(&bctr[qsel & 3u], 1u);
     // FUSED: the workgroup's next block, or its first one again for the next tick; none after the last tick
     // (computed where it is used, from values that are at hand anyway: held through the block it cost a spill)
     const auto next_block = [&]() -> uint64_t {
-      const uint64_t b = blk + gridDim.x;
-      return b < nblk ? b : (tick + 1u < ticks ? (uint64_t)blockIdx.x : nblk);
+      const uint64_t b = blk + 1u;
+      return b < bend ? b : (tick + 1u < ticks ? b0 : nblk);
     };
     // the per-lane values derive from an opaque copy of the lane id, block by block: hoisted out of
     // the loop, they and what the compiler derives from them would hold registers through every
@@ -3696,7 +3756,7 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
     const int slot = tid_o;
     uint32_t* plan_w = lds + (env_wave ? slot : 0) * pdw;
     Plan pl{reinterpret_cast<uint16_t*>(plan_w)};
-    const uint64_t env0 = blk * (uint64_t)L.envs;
+    const uint64_t env0 = phys(blk) * (uint64_t)L.envs;  // (FUSED: blk is the place in the workgroup's range)
     const int nb = (int)min((uint64_t)L.envs, S.n - env0);
     const uint64_t i = env0 + slot;
     const bool live = env_wave && slot < nb;
@@ -3757,7 +3817,7 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
       // (an env's byte is written and read by the same lane, tick after tick: in order.  A workgroup
       // that owns one block would read it here before this tick's store: it reads it behind that store.)
       const uint64_t bn = next_block();
-      const uint64_t ni = bn * (uint64_t)L.envs + (uint64_t)slot;
+      const uint64_t ni = (bn < nblk ? phys(bn) : bn) * (uint64_t)L.envs + (uint64_t)slot;
       qs_nx = 0;
       if (bn != blk && bn < nblk && slot < L.envs && ni < S.n) qs_nx = S.qstate[ni];
     } else {
@@ -3770,7 +3830,7 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
       write_obs(out.final_obs + env0 * (uint64_t)c.obs_bytes, (uint32_t)nb, (uint32_t)c.obs_bytes, st, sel, rank, nthr, lm);
     STAMP(3);
     sub_barrier(ctr, bar += (uint32_t)np);  // terminal images written before they are rebuilt
-    if (FUSED && tick > 0 && blk == blockIdx.x) {
+    if (FUSED && tick > 0 && blk == b0) {
       // the tick's first ring take: the helper has stored the fills it made during the tick before
       // (requested two ticks back, the youngest entries a take can meet).  It started on them when
       // this wave arrived at that tick's start, so the wait is for nothing later than this tick.
@@ -3846,7 +3906,7 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
     // (the same lane, the same address: in order; kept in a register from the take it cost a spill).  This
     // load is younger than the wait above, which does not cover it: the byte is next used after the tick's
     // boundary, at the staging of this block again, and waited for there.  On the last tick it is read for nothing.
-    if (FUSED && blk == blockIdx.x && blk + gridDim.x >= nblk && live) qs_nx = S.qstate[i];
+    if (FUSED && bc == 1u && live) qs_nx = S.qstate[i];
     if (live) {
       rec_store(S.rec, i, v);
       S.err[i] = (uint8_t)(-err);
@@ -3867,19 +3927,21 @@ __global__ void __launch_bounds__(kBlock, 4) k_envq(const DevCfg* __restrict__ c
       write_obs(out.obs + env0 * (uint64_t)c.obs_bytes, (uint32_t)nb, (uint32_t)c.obs_bytes, st, nullptr, rank, nthr, om);
     if (om) om = om == om0 ? om0 + L.lm_words : om0;  // (the other mask: see kObsMasks)
     if (tid == 0) atomicAdd(&S.counters[0], (unsigned long long)nb);
-    if (blk == blockIdx.x && (!FUSED || tick == 0)) stagger_record(L, S, t_start);
+    if (blk == b0 && (!FUSED || tick == 0)) stagger_record(L, S, t_start);
     STAMP(6);
     if (!FUSED) {
       blk = g == 0xffffffffu ? nblk : (uint64_t)gridDim.x + g;
       continue;
     }
     const uint64_t blk_nx = next_block();
-    if (blk + gridDim.x >= nblk) STAMPT(tick);  // (the tick's last block of this workgroup)
-    if (blk_nx > blk) {
+    if (blk + 1u >= bend) STAMPT(tick);  // (the tick's last block of this workgroup)
+    if (blk + 1u < bend) {
       blk = blk_nx;
       continue;
     }
-    // FUSED, the tick's last block (more ticks follow): its requests and their count are stored --
+    // the workgroup's wall clock at the end of its last tick's last block, before the helper's drain
+    if (tick + 1u == ticks && tid == 0) wgw[kWgWords * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
+    // FUSED, the tick's last block (the helper's drain follows the last tick): its requests and their count are stored --
     // tid 0's store above is behind the block's last barrier, hence behind every wave's requests --
     // which each wave publishes to the helper as it arrives; none waits here.  The next tick writes the
     // other list and counts from zero: nothing touches *qn before that tick's first barrier, and its
@@ -4363,6 +4425,126 @@ __global__ void __launch_bounds__(kBlock) k_squares(const DevCfg* __restrict__ c
   }
 }
 
+// The maps the last k_envq<BIG, true> launch's drain made, into counters[2]: queued ahead of whatever next serves or
+// drops request lists (a step launch, queue_fill), which is where a launch per tick makes and counts them.  Ahead of
+// a reset (`mask`: the envs it resets, nullptr: all) the requests of the envs reset do not count: a launch per
+// tick drops them there, and the reset's ring fill makes those envs' next two maps on either path.
+// One wave per workgroup of the queue grid walks the list that workgroup's drain served (parity `par`).
+__global__ void __launch_bounds__(64) k_drained(const uint2* __restrict__ qreq, unsigned long long* wgw, uint64_t cap,
+                                                uint32_t par, const uint8_t* __restrict__ mask, bool reset,
+                                                unsigned long long* counters) {
+  const uint32_t n = (uint32_t)min((unsigned long long)cap, wgw[kWgWords * blockIdx.x + 2]);
+  if (n == 0) return;
+  const uint2* list = qreq + ((uint64_t)par * gridDim.x + blockIdx.x) * cap;
+  uint32_t c = 0;
+  for (uint32_t k = threadIdx.x; k < n; k += 64)
+    if (!reset || (mask && mask[list[k].x >> 2] == 0)) c++;
+  c = wave_sum(c);
+  if (threadIdx.x == 0) {
+    if (c) atomicAdd(&counters[2], (unsigned long long)c);
+    wgw[kWgWords * blockIdx.x + 2] = 0ull;
+  }
+}
+
+// The block shares of k_envq<BIG, true>'s next launch from the clocks of the last (the rule's pieces are
+// pgtg_shares.h's, one lane per workgroup here).  One workgroup, queued behind the launch on its stream.
+// own: own_start[grid], own_count[grid]; clk: [grid][kWgWords], the wall clocks first; est: [grid] running time per block, est[grid]
+// nonzero once there are estimates; rem: [grid] scratch.  Whatever the clocks hold, the counts it leaves sum to nblk
+// inside the clamps and the starts are their prefix sums.
+constexpr int kSharesBlock = 1024;
+__global__ void __launch_bounds__(kSharesBlock) k_shares(uint32_t* own, const unsigned long long* clk, uint32_t* est,
+                                                        unsigned long long* rem, uint32_t grid, uint64_t nblk,
+                                                        uint32_t ticks, uint64_t cap_blocks) {
+  __shared__ uint64_t key[kMaxQueueGrid];
+  __shared__ unsigned long long sW, sM;
+  __shared__ uint32_t sN, sSum, sMoved;
+  const uint32_t tid = threadIdx.x;
+  uint32_t* cnt = own + grid;
+  const uint32_t lo = share_lo(nblk, grid), hi = share_hi(nblk, grid, cap_blocks);
+  if (tid == 0) {
+    sW = sM = 0ull;
+    sN = sSum = sMoved = 0u;
+  }
+  __syncthreads();
+  for (uint32_t i = tid; i < grid; i += kSharesBlock) {
+    const uint32_t c = cnt[i];
+    const unsigned long long t0 = clk[kWgWords * i], t1 = clk[kWgWords * i + 1];
+    const uint32_t m = (c && t1 > t0) ? share_measure(t1 - t0, ticks, c) : 0u;
+    key[i] = m;
+    if (m) {
+      atomicAdd(&sM, (unsigned long long)m);
+      atomicAdd(&sN, 1u);
+    }
+  }
+  __syncthreads();
+  const bool first = est[grid] == 0u;
+  const uint32_t e0 = sN ? (uint32_t)(sM / sN) : 1u;  // equal speeds, at the scale measured
+  __syncthreads();
+  for (uint32_t i = tid; i < grid; i += kSharesBlock) {
+    const uint32_t m = (uint32_t)key[i];
+    uint32_t e = first ? e0 : est[i];
+    if (m) e = share_blend(e, m);  // (a workgroup without blocks keeps its estimate)
+    est[i] = e;
+    atomicAdd(&sW, (unsigned long long)share_weight(e));
+  }
+  if (tid == 0) est[grid] = 1u;
+  __syncthreads();
+  const uint64_t W = sW;
+  uint32_t mine[kMaxQueueGrid / kSharesBlock];
+#pragma unroll
+  for (uint32_t k = 0; k < kMaxQueueGrid / kSharesBlock; k++) {
+    const uint32_t i = tid + k * kSharesBlock;
+    mine[k] = 0;
+    if (i < grid) {
+      uint64_t r;
+      mine[k] = share_quota(nblk, share_weight(est[i]), W, lo, hi, &r);
+      rem[i] = r;
+      atomicAdd(&sSum, mine[k]);
+    }
+  }
+  __syncthreads();
+  int64_t left = (int64_t)nblk - (int64_t)sSum;
+  for (int pass = 0; pass < kSharePasses && left != 0; pass++) {  // (left is the same in every lane)
+    const bool up = left > 0;
+    const uint64_t want = (uint64_t)(up ? left : -left);
+#pragma unroll
+    for (uint32_t k = 0; k < kMaxQueueGrid / kSharesBlock; k++) {
+      const uint32_t i = tid + k * kSharesBlock;
+      if (i < grid) key[i] = share_key(up, mine[k], rem[i], W, lo, hi);
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < kMaxQueueGrid / kSharesBlock; k++) {
+      const uint32_t i = tid + k * kSharesBlock;
+      if (i < grid && key[i] && share_rank(up, key, grid, i) < want) {
+        mine[k] += up ? 1u : ~0u;
+        atomicAdd(&sMoved, 1u);
+      }
+    }
+    __syncthreads();
+    left += up ? -(int64_t)sMoved : (int64_t)sMoved;
+    __syncthreads();
+    if (tid == 0) sMoved = 0u;
+    __syncthreads();
+  }
+  // the counts (equal shares should the clamps ever admit none: the table always covers the blocks once), then
+  // the starts, their prefix sums
+  uint32_t* c32 = reinterpret_cast<uint32_t*>(key);
+  __syncthreads();
+#pragma unroll
+  for (uint32_t k = 0; k < kMaxQueueGrid / kSharesBlock; k++) {
+    const uint32_t i = tid + k * kSharesBlock;
+    if (i < grid) c32[i] = left == 0 ? mine[k] : (uint32_t)(nblk / grid) + (i < nblk % grid ? 1u : 0u);
+  }
+  __syncthreads();
+  for (uint32_t i = tid; i < grid; i += kSharesBlock) {
+    uint32_t s = 0;
+    for (uint32_t j = 0; j < i; j++) s += c32[j];
+    own[i] = s;
+    cnt[i] = c32[i];
+  }
+}
+
 __global__ void k_random_actions(uint8_t* a, uint64_t n, uint64_t seed, uint64_t t, uint64_t offset) {
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -4758,6 +4940,18 @@ struct pgtg_handle {
   uint32_t step_ticks = kStepTicks;
   uint64_t step_kernels = 0;  // step-kernel launches so far, whatever their ticks (pgtg_get_step_launches)
   bool q_static = false;
+  // k_envq<BIG, true>'s block shares, all on the device: own_start[q_grid] then own_count[q_grid],
+  // contiguous ranges covering the blocks once; the workgroups' start and end clocks of the last launch; k_shares'
+  // running time per block (and whether it has any), and its scratch.  own_blocks: the block count the table covers.
+  // own_frozen: pgtg_set_block_shares stopped k_shares.  q_drained: a launch's drain may have left maps to count.
+  uint32_t* own = nullptr;
+  unsigned long long* own_clk = nullptr;
+  uint32_t* own_est = nullptr;
+  unsigned long long* own_rem = nullptr;
+  uint64_t own_blocks = 0, own_grid = 0;
+  uint32_t q_drained_par = 0;  // the parity of the lists the last launch's drains served
+  bool own_frozen = false;
+  bool q_drained = false;
   // The bound obs buffer holds every env's current observation: set by a launch that wrote them all,
   // cleared by whatever changes an env's state, the output binding or the step kernel without rewriting
   // them.  k_envq then writes only the lines of the observations that changed (obs_key).
@@ -4872,6 +5066,32 @@ static int cu_count(int device) {
 static int host_sync(pgtg_handle* h) {
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// k_envq<BIG, true>'s share table from counts (q_grid of them, summing to the handle's blocks): the starts are their
+// prefix sums.  The stream is drained first: no launch reads the table while it changes.
+static int upload_shares(pgtg_handle* h, const uint32_t* counts) {
+  if (int rc = host_sync(h)) return rc;
+  std::vector<uint32_t> t(2 * h->q_grid);
+  uint32_t s = 0;
+  for (uint64_t w = 0; w < h->q_grid; w++) {
+    t[w] = s;
+    t[h->q_grid + w] = counts[w];
+    s += counts[w];
+  }
+  HIPCHK(h, hipMemcpy(h->own, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  h->own_blocks = s;
+  h->own_grid = h->q_grid;
+  return 0;
+}
+// equal shares (the first nblk % grid workgroups one block more), and k_shares' estimates forgotten
+static int equal_shares(pgtg_handle* h) {
+  const uint64_t blocks = (h->n + h->L.envs - 1) / h->L.envs;
+  std::vector<uint32_t> c(h->q_grid);
+  for (uint64_t w = 0; w < h->q_grid; w++) c[w] = (uint32_t)(blocks / h->q_grid + (w < blocks % h->q_grid ? 1 : 0));
+  if (int rc = upload_shares(h, c.data())) return rc;
+  HIPCHK(h, hipMemset(h->own_est, 0, (h->q_grid + 1) * sizeof(uint32_t)));
   return 0;
 }
 
@@ -5352,6 +5572,9 @@ static int create(pgtg_handle* h, const PgtgConfig* cfg) {
   if (cfg->tune_step_ticks > 0) h->step_ticks = (uint32_t)cfg->tune_step_ticks;
 #ifdef PGTG_TUNING
   if (const char* e = getenv("PGTG_STEP_TICKS")) h->step_ticks = (uint32_t)std::max(1, atoi(e));
+  // PGTG_SHARES=0: equal frozen block shares, k_shares never queued -- pgtg_set_block_shares(NULL, 0, 1) for a caller
+  // that cannot reach the hook (bench.py in tools/ab_trees.sh: the A/B step "drain")
+  if (const char* e = getenv("PGTG_SHARES")) h->own_frozen = atoi(e) == 0;
 #endif
   if (h->n == 0) return fail(h, PGTG_E_INVALID, "n_envs must be > 0");
   if (int rc = derive_cfg(h, *cfg, h->hcfg)) return rc;
@@ -5473,7 +5696,13 @@ static int create(pgtg_handle* h, const PgtgConfig* cfg) {
     const uint64_t blocks = (n + h->L.envs - 1) / h->L.envs;
     if (int rc = dalloc(h, &S.qreq, 2 * h->q_grid * queue_req_cap(blocks, h->q_grid, h->L.envs))) return rc;
     if (int rc = dalloc(h, &S.qovf, 2 * 8 * ((h->q_grid + 7) / 8) * (uint64_t)h->L.envs)) return rc;
-    if (int rc = dalloc(h, &S.qctr, kQctrWords)) return rc;
+    if (int rc = dalloc(h, &S.qctr, kQctrAlloc)) return rc;
+    // k_envq<BIG, true>'s block shares: the table, the workgroups' clocks, k_shares' estimates
+    h->own = S.qctr + kQctrOwn;  // (in the counters' allocation: the step kernels take no further argument)
+    h->own_clk = reinterpret_cast<unsigned long long*>(S.qctr + kQctrWg);
+    if (int rc = dalloc(h, &h->own_est, h->q_grid + 1)) return rc;
+    if (int rc = dalloc(h, &h->own_rem, h->q_grid)) return rc;
+    if (int rc = equal_shares(h)) return rc;
   }
   return PGTG_OK;
 }
@@ -5583,8 +5812,21 @@ static int launch_flatten(pgtg_handle* h, int mode, uint64_t grid) {
   return PGTG_OK;
 }
 
+// The maps the last multi-tick launch's drain made are counted from here on (k_drained).
+static int count_drained(pgtg_handle* h, bool reset = false, const uint8_t* mask = nullptr) {
+  if (!h->q_drained) return PGTG_OK;
+  h->q_drained = false;
+  const uint64_t blocks = (h->n + h->L.envs - 1) / h->L.envs;
+  hipLaunchKernelGGL(k_drained, dim3((unsigned)h->own_grid), dim3(64), 0, h->stream, h->S.qreq, h->own_clk,
+                     queue_req_cap(blocks, h->own_grid, h->L.envs), h->q_drained_par, mask, reset, h->S.counters);
+  HIPCHK(h, hipGetLastError());
+  return PGTG_OK;
+}
+
 static int launch(pgtg_handle* h, const uint8_t* actions, const uint8_t* mask, int mode) {
   HIPCHK(h, hipSetDevice(h->device));
+  if (mode != MODE_OBSERVE)
+    if (int rc = count_drained(h, mode != MODE_STEP, mask)) return rc;
   uint64_t blocks = (h->n + h->L.envs - 1) / h->L.envs;
   const bool timed = h->timing > 0 && mode == MODE_STEP && (h->step_launches++ % (uint64_t)h->timing) == 0;
   if (timed) {
@@ -5651,6 +5893,7 @@ static int launch(pgtg_handle* h, const uint8_t* actions, const uint8_t* mask, i
 // and the rings of the envs a reset gave new maps.
 static int queue_fill(pgtg_handle* h) {
   if (!h->L.queue || !h->S.qbuf) return PGTG_OK;
+  if (int rc = count_drained(h)) return rc;
   if (h->S.qctr) HIPCHK(h, hipMemsetAsync(h->S.qctr, 0, kQctrWords * sizeof(uint32_t), h->stream));
   h->q_static = true;  // (no request pending)
 #ifdef PGTG_TUNING
@@ -5722,15 +5965,29 @@ static int launch_many(pgtg_handle* h, const uint8_t* actions, uint64_t row_stri
     return fail(h, PGTG_E_INVALID, "launch_many on a handle that needs a launch per tick");
   HIPCHK(h, hipSetDevice(h->device));
   const StepKernel& k = kStepKernels[2 * ENVQ_MANY + (h->hcfg.nt > kSmallTiles ? 0 : 1)];
+  const uint64_t blocks = (h->n + h->L.envs - 1) / h->L.envs;
+  if (int rc = count_drained(h)) return rc;
+  if (h->own_grid != h->q_grid)  // (the table, the lists and the clocks were sized for the grid at create)
+    return fail(h, PGTG_E_INVALID, "k_envq<BIG, true>: the queue grid changed since create");
+  if (h->own_blocks != blocks)  // (another layout since the table was made: equal shares again)
+    if (int rc = equal_shares(h)) return rc;
   const bool full = !h->obs_current;  // (the first tick writes every observation line)
   h->obs_current = false;
   uint32_t qsel = (uint32_t)(h->q_launch % 3) | (uint32_t)(h->q_launch & 1) << 2 | (full ? kQselFull : 0u);
   void* args[] = {&h->dcfg, &h->dtab, &h->S, &actions, &h->out, &h->L, &qsel, &ticks, &row_stride};
   h->q_launch += ticks;  // (the lists rotate per tick inside the kernel, by the rule of launch())
   h->step_kernels++;
-  h->q_static = true;
+  h->q_static = true;  // (the drain leaves the lists empty)
+  h->q_drained = true;
+  h->q_drained_par = (uint32_t)((h->q_launch - 1) & 1);  // (the last tick's list)
   HIPCHK(h, hipLaunchKernel(k.fn, dim3((unsigned)h->q_grid), dim3(kBlock), args, h->lds, h->stream));
   HIPCHK(h, hipGetLastError());
+  if (ticks > 1 && !h->own_frozen) {  // the next launch's shares, from this one's clocks
+    const uint64_t capb = queue_req_cap(blocks, h->q_grid, h->L.envs) / (uint64_t)h->L.envs;
+    hipLaunchKernelGGL(k_shares, dim3(1), dim3(kSharesBlock), 0, h->stream, h->own, h->own_clk, h->own_est, h->own_rem,
+                       (uint32_t)h->q_grid, blocks, ticks, capb);
+    HIPCHK(h, hipGetLastError());
+  }
   h->obs_current = h->out.obs != nullptr;
   return PGTG_OK;
 }
@@ -6191,6 +6448,9 @@ int pgtg_load_state(pgtg_handle* h, const void* buf, uint64_t bytes) {
   }
   if (h->S.tr_count) HIPCHK(h, hipMemset(h->S.tr_count, 0, 2 * sizeof(uint32_t)));
   if (h->S.qctr) HIPCHK(h, hipMemset(h->S.qctr, 0, kQctrWords * sizeof(uint32_t)));  // (dumped with full rings)
+  // (a drain's maps not yet counted served requests that a launch per tick drops here)
+  if (h->q_drained) HIPCHK(h, hipMemset(h->own_clk, 0, kWgWords * h->own_grid * sizeof(unsigned long long)));
+  h->q_drained = false;
   if (h->ep.ret) {  // the episode accumulators are not in the blob: every env starts a new count
     HIPCHK(h, hipMemsetAsync(h->ep.ret, 0, h->n * sizeof(float), h->stream));  // (ordered with k_episode)
     HIPCHK(h, hipMemsetAsync(h->ep.len, 0, h->n * sizeof(int32_t), h->stream));
@@ -6400,6 +6660,36 @@ int pgtg_get_counters(pgtg_handle* h, uint64_t* env_steps, uint64_t* episodes) {
   if (int rc = read_counters(h, c)) return rc;
   if (env_steps) *env_steps = c[0];
   if (episodes) *episodes = c[1];
+  return PGTG_OK;
+}
+
+int pgtg_set_block_shares(pgtg_handle* h, const uint32_t* counts, uint32_t n, int32_t freeze) {
+  if (!h) return PGTG_E_INVALID;
+  if (!h->own) return fail(h, PGTG_E_INVALID, "block shares: not a k_envq handle");
+  const uint64_t blocks = (h->n + h->L.envs - 1) / h->L.envs;
+  if (counts) {
+    const uint64_t capb = queue_req_cap(blocks, h->q_grid, h->L.envs) / (uint64_t)h->L.envs;
+    uint64_t sum = 0;
+    if (n != h->q_grid) return fail(h, PGTG_E_INVALID, "block shares: one count per workgroup of the queue grid");
+    for (uint32_t w = 0; w < n; w++) {
+      if (counts[w] > capb) return fail(h, PGTG_E_INVALID, "block shares: a count above the request lists' capacity");
+      sum += counts[w];
+    }
+    if (sum != blocks) return fail(h, PGTG_E_INVALID, "block shares: the counts do not sum to the blocks");
+    if (int rc = upload_shares(h, counts)) return rc;
+  }
+  h->own_frozen = freeze != 0;
+  return PGTG_OK;
+}
+
+int pgtg_get_block_shares(pgtg_handle* h, uint32_t* counts, uint32_t n, uint32_t* grid) {
+  if (!h) return PGTG_E_INVALID;
+  if (!h->own) return fail(h, PGTG_E_INVALID, "block shares: not a k_envq handle");
+  if (grid) *grid = (uint32_t)h->q_grid;
+  if (!counts) return PGTG_OK;
+  if (n != h->q_grid) return fail(h, PGTG_E_INVALID, "block shares: one count per workgroup of the queue grid");
+  if (int rc = host_sync(h)) return rc;
+  HIPCHK(h, hipMemcpy(counts, h->own + h->q_grid, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return PGTG_OK;
 }
 

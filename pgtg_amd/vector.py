@@ -694,6 +694,26 @@ class PGTGVecEnv:
         _check(self._lib.pgtg_get_step_launches(self._h, C.byref(m)), self._h)
         return m.value
 
+    def block_shares(self):
+        """Blocks per workgroup of the multi-tick step launches (uint32 numpy array, one per workgroup of the
+        queue grid; include/pgtg.h pgtg_get_block_shares).  k_envq handles only."""
+        import numpy as np
+        g = C.c_uint32()
+        _check(self._lib.pgtg_get_block_shares(self._h, None, 0, C.byref(g)), self._h)
+        out = np.zeros(g.value, np.uint32)
+        _check(self._lib.pgtg_get_block_shares(self._h, C.c_void_p(out.ctypes.data), g.value, None), self._h)
+        return out
+
+    def set_block_shares(self, counts=None, freeze: bool = True) -> None:
+        """Force the block shares (tuning and tests; include/pgtg.h pgtg_set_block_shares): `counts` per workgroup
+        or None to keep them; `freeze` stops the device-side update."""
+        import numpy as np
+        if counts is None:
+            _check(self._lib.pgtg_set_block_shares(self._h, None, 0, int(bool(freeze))), self._h)
+            return
+        c = np.ascontiguousarray(counts, dtype=np.uint32)
+        _check(self._lib.pgtg_set_block_shares(self._h, C.c_void_p(c.ctypes.data), c.size, int(bool(freeze))), self._h)
+
     def queue_overflow(self) -> int:
         """Map-queue refill requests served from the one-round overflow lists since create."""
         m = C.c_uint64()

@@ -21,7 +21,8 @@ from pgtg_amd import _abi  # noqa: E402
 _abi.LIB_PATH = os.environ.get("PGTG_STAMPS_LIB") or os.path.join(os.path.dirname(_abi.LIB_PATH), "libpgtg_hip_stamps.so")
 from pgtg_amd.vector import PGTGVecEnv  # noqa: E402
 
-SLOTS = 32
+from stamp_layout import REAL_BASE, REAL_ROW, SLOTS, TICK_BASE, TICK_ROW  # noqa: E402
+
 PHASES = ["stage", "step", "final", "reset", "store", "obs"]
 SUB = {"cars": (16, 17), "braking": (17, 18), "reset.seed": (8, 9), "reset.generate": (9, 10),
        "reset.compile": (10, 11), "path.masks": (10, 24), "path.bfs": (24, 25), "path.walk": (25, 11), "reset.start": (11, 12), "gen.start_goal": (9, 13), "gen.edge_init": (13, 14),
@@ -56,7 +57,7 @@ for name in (sys.argv[1:] or ["cfg2", "cfg5"]):
     torch.cuda.synchronize()
     blocks = (N + E - 1) // E
     nw = blocks * 4
-    buf = np.zeros(max(nw * SLOTS, (1 << 20) + 8 * nw), np.uint64)
+    buf = np.zeros(max(nw * SLOTS, REAL_BASE + REAL_ROW * nw), np.uint64)
     _abi.lib().pgtg_read_stamps.argtypes = [C.c_void_p, C.c_uint64]
     _abi.lib().pgtg_read_stamps(buf.ctypes.data, buf.size)
     st = buf[:nw * SLOTS].reshape(nw, SLOTS).astype(np.int64)
@@ -114,7 +115,7 @@ for name in (sys.argv[1:] or ["cfg2", "cfg5"]):
             epi = st[ok, 24] - st[ok, 23]
             body = st[ok, 23] - st[ok, 19]
             q = lambda a: (int(a.mean()), int(np.percentile(a, 90)), int(a.max()))  # noqa: E731
-            rt = buf[1 << 20:(1 << 20) + 8 * nw].reshape(nw, 8).astype(np.int64)
+            rt = buf[REAL_BASE:REAL_BASE + REAL_ROW * nw].reshape(nw, REAL_ROW).astype(np.int64)
             e_end, t_beg = rt[:, 0], rt[rt[:, 1] > 0, 1]
             print("  wall clock (10 ns ticks): k_env waves end", 0, "..", int(e_end.max() - e_end.min()),
                   "; k_traffic waves start", int(t_beg.min() - e_end.min()), "..", int(t_beg.max() - e_end.min()), flush=True)
@@ -124,7 +125,7 @@ for name in (sys.argv[1:] or ["cfg2", "cfg5"]):
                   "(the traffic_reset stamps are the last round's)", flush=True)
             print("  k_traffic waves (mean, p90, max): total", q(tot), "before the last round", q(pro),
                   "last round's traffic_reset", q(body), "epilogue", q(epi), flush=True)
-    rt = buf[1 << 20:(1 << 20) + 8 * nw].reshape(nw, 8).astype(np.int64)
+    rt = buf[REAL_BASE:REAL_BASE + REAL_ROW * nw].reshape(nw, REAL_ROW).astype(np.int64)
     okw = (rt[:, 2] > 0) & (rt[:, 3] > rt[:, 2])
     if not spread and okw.any():  # k_envq: wall-clock start and end of every wave (10 ns ticks, one clock)
         wid = np.arange(nw)[okw]
@@ -138,7 +139,7 @@ for name in (sys.argv[1:] or ["cfg2", "cfg5"]):
               "writer-wave ends", q(end[~ew & ~hw]) if (~ew & ~hw).any() else None, flush=True)
     if T and not spread and okw.any():  # the tick dimension of the last launch (k_envq<BIG, true>, T ticks)
         wgs = int(wid.max()) // 4 + 1
-        tt = buf[(1 << 19):(1 << 19) + 256 * wgs].reshape(wgs, 256)[:, :T].astype(np.int64)
+        tt = buf[TICK_BASE:TICK_BASE + TICK_ROW * wgs].reshape(wgs, TICK_ROW)[:, :T].astype(np.int64)
         beg0 = rt[0:4 * wgs:4, 2]  # wave 0's start
         if (tt > 0).all():
             ends = tt - t0
