@@ -18,6 +18,8 @@
  *                        wrapper the reference's caller puts around the vector env  pgtg/train.py:55
  *   pgtg_gae          <- (new, no reference function) RolloutBuffer.compute_returns_and_advantage of the
  *                        PPO the reference's caller trains                 pgtg/train.py:61-74
+ *   pgtg_set_flat_cost / pgtg_cost_scan <- info["cost"] of separate_reward_cost through the rollout, and
+ *                        a Lagrange multiplier on it (new past the step)  environment.py:1130-1276
  *   pgtg_policy / pgtg_policy_pack <- (new, no reference function) the acting forward pass of the
  *                        MlpPolicy that PPO collects with                  pgtg/train.py:61-74
  *   pgtg_eval_step / pgtg_eval_summary <- ModularEvaluator.evaluate for the batch, with the per-env
@@ -309,6 +311,12 @@ int pgtg_set_flat_outputs(pgtg_handle* h, const int32_t* order, int32_t n_order,
  * vector env returns -- into these [N] device buffers (all three or none; needs the reward, terminated
  * and truncated outputs bound).  No reference function: it replaces per-step tensor arithmetic. */
 int pgtg_set_flat_scalars(pgtg_handle* h, float* reward_f32_dev, uint8_t* dones_dev, uint8_t* truncated_only_dev);
+/* With the flat scalars bound, the same pass also writes the cost of separate_reward_cost (info["cost"],
+ * environment.py:1130-1276) as float32, (float)cost[e], into this [N] device buffer.  NULL unbinds.  Valid only
+ * on a handle created with separate_reward_cost whose cost output is bound, and only while the scalars of
+ * pgtg_set_flat_scalars are bound: PGTG_E_INVALID with a message otherwise, and nothing changes.
+ * pgtg_set_flat_scalars(NULL, NULL, NULL) unbinds the cost too; rebinding the three scalars keeps it. */
+int pgtg_set_flat_cost(pgtg_handle* h, float* cost_f32_dev);
 /* k_flatten alone, over the bound outputs as they are now (tests: rows from chosen inputs, without a
  * step, reset or observe launch rewriting the observation first).  mode: 0 the observation rows and
  * the scalars of pgtg_set_flat_scalars, 1 the terminal rows of the envs whose terminated | truncated
@@ -365,6 +373,46 @@ typedef struct {
   float* advantages; float* returns;   /* [T][N] */
 } PgtgGae;
 int pgtg_gae(pgtg_handle* h, const PgtgGae* a);
+/* The safety cost of a device-resident rollout of N envs and T steps (new; no reference function: the
+ * reference returns info["cost"] per step and leaves the rest to its caller): per-episode cost sums, the
+ * Lagrangian penalty on the reward (RCPO, Tessler et al. 2018) and the dual ascent of the multiplier on the mean
+ * episode cost against a budget.  Two launches.  k_cost_scan, one lane per env, no fused multiply-add, with
+ * lam = *lambda as it stood before the call, acc = ep_cost[e], t = 0 .. T-1:
+ *   penalised[t][e] = rewards[t][e] - lam * costs[t][e]      (float32: the product rounds, then the difference)
+ *   acc += (double)costs[t][e]
+ *   dones[t+1][e] != 0:  the episode joins the summary with cost acc;  acc = 0
+ *   ep_cost[e] = acc  (after row T-1: the cost of the episode under way, carried into the next rollout)
+ * then k_cost_dual, one workgroup, which writes *summary and, with episodes > 0, in fp64
+ *   cost_mean = cost_sum / episodes;  l = (double)lam + lambda_lr * (cost_mean - cost_limit)
+ *   *lambda = (float)min(max(l, 0), lambda_max)
+ * (episodes == 0: cost_mean = cost_max = 0 and the word is left as it is).  cost_sum runs in one order, a
+ * function of N alone (per env in step order, 256 envs per workgroup by a shuffle tree and wave order, the
+ * workgroups' rows in row order; no atomics): the same arrays give the same bits on any device.  penalised is
+ * what pgtg_gae then takes as its rewards.  All pointers are device pointers; ep_cost, summary and workspace
+ * (pgtg_cost_workspace_bytes(n) bytes, contents irrelevant) 8-byte aligned.  The handle is used for its device,
+ * stream and error string only.  steps == 0, a NULL or misaligned pointer, a non-finite cost_limit or
+ * lambda_lr, lambda_max < 0 or NaN: PGTG_E_INVALID; a rollout beyond one launch (pgtg_gae's limits):
+ * PGTG_E_UNSUPPORTED; each with a message, nothing launched.  n == 0 is a no-op.  Asynchronous on the
+ * handle's stream. */
+typedef struct {
+  uint64_t episodes;                       /* episodes that ended inside the rollout */
+  double cost_sum, cost_mean, cost_max;    /* of their costs */
+  float lambda_before, lambda_after;       /* the multiplier the rollout was penalised with, and the next */
+} PgtgCostSummary;
+typedef struct {
+  uint64_t n, steps;
+  const float*   rewards;     /* [T][N] */
+  const float*   costs;       /* [T][N] (k_flatten's scalar of pgtg_set_flat_cost) */
+  const uint8_t* dones;       /* [T+1][N]: row t+1 = the episode ended in step t */
+  double* ep_cost;            /* [N] carry: cost of the episode under way (in/out) */
+  float*  penalised;          /* [T][N] out */
+  float*  lambda;             /* device word, in/out */
+  double cost_limit, lambda_lr, lambda_max;
+  PgtgCostSummary* summary;   /* device, out */
+  void* workspace;
+} PgtgCost;
+int pgtg_cost_workspace_bytes(uint64_t n, uint64_t* bytes);
+int pgtg_cost_scan(pgtg_handle* h, const PgtgCost* a);
 /* The acting forward pass of SB3's MlpPolicy over int8 flat rows (new; no reference function: it replaces
  * ActorCriticPolicy.forward / predict_values of the PPO("MlpPolicy") of pgtg/train.py:61-74 inside
  * collect_rollouts).  Separate pi / vf towers, 64-64, tanh, 9 actions; float32 throughout.  Per env e,

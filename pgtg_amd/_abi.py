@@ -34,6 +34,7 @@ EXPORTED = [
     "pgtg_timing_read", "pgtg_measure_hbm", "pgtg_state_size", "pgtg_dump_state", "pgtg_load_state",
     "pgtg_set_to_state", "pgtg_car_digest", "pgtg_get_queue_maps", "pgtg_get_step_launches", "pgtg_set_block_shares", "pgtg_get_block_shares", "pgtg_get_queue_overflow", "pgtg_set_flat_outputs", "pgtg_set_flat_scalars",
     "pgtg_set_episode_stats", "pgtg_episode_summary", "pgtg_gae", "pgtg_flatten",
+    "pgtg_set_flat_cost", "pgtg_cost_workspace_bytes", "pgtg_cost_scan",
     "pgtg_eval_step", "pgtg_eval_summary", "pgtg_eval_workspace_bytes",
     "pgtg_policy", "pgtg_policy_pack", "pgtg_policy_packed_bytes", "pgtg_policy_chunk",
     "pgtg_ppo_workspace_bytes", "pgtg_ppo_grad",
@@ -106,6 +107,18 @@ class PgtgGae(C.Structure):
     _fields_ = [("n", C.c_uint64), ("steps", C.c_uint64), ("gamma", C.c_double), ("gae_lambda", C.c_double)] + [
         (n, C.c_void_p) for n in ("rewards", "values", "dones", "truncated_only", "terminal_values", "last_values",
                                   "advantages", "returns")]
+
+
+class PgtgCostSummary(C.Structure):
+    _fields_ = [("episodes", C.c_uint64), ("cost_sum", C.c_double), ("cost_mean", C.c_double), ("cost_max", C.c_double),
+                ("lambda_before", C.c_float), ("lambda_after", C.c_float)]
+
+
+class PgtgCost(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("steps", C.c_uint64)] + [
+        (n, C.c_void_p) for n in ("rewards", "costs", "dones", "ep_cost", "penalised", "lambda_")] + [
+        ("cost_limit", C.c_double), ("lambda_lr", C.c_double), ("lambda_max", C.c_double),
+        ("summary", C.c_void_p), ("workspace", C.c_void_p)]
 
 
 EVAL_STATE_FIELDS = ("ret", "disc", "g", "len", "cnt")
@@ -228,6 +241,9 @@ def lib():
         "pgtg_set_episode_stats": ([vp, vp, vp], C.c_int),
         "pgtg_episode_summary": ([vp, C.POINTER(PgtgEpisodeSummary), i32], C.c_int),
         "pgtg_gae": ([vp, C.POINTER(PgtgGae)], C.c_int),
+        "pgtg_set_flat_cost": ([vp, vp], C.c_int),
+        "pgtg_cost_workspace_bytes": ([u64, C.POINTER(u64)], C.c_int),
+        "pgtg_cost_scan": ([vp, C.POINTER(PgtgCost)], C.c_int),
         "pgtg_eval_step": ([vp, C.POINTER(PgtgEval)], C.c_int),
         "pgtg_eval_summary": ([vp, C.POINTER(PgtgEval), vp, vp], C.c_int),
         "pgtg_eval_workspace_bytes": ([u64, u64, C.POINTER(u64)], C.c_int),

@@ -29,6 +29,7 @@
 #include "pgtg_episode.h"
 #include "pgtg_eval.h"
 #include "pgtg_rollout.h"
+#include "pgtg_cost.h"
 #include "pgtg_policy.h"
 #include "pgtg_ppo.h"
 #include "pgtg_ppo_step.h"
@@ -4629,11 +4630,14 @@ struct FlatArgs {
   const uint8_t* trunc;
   void* dst;
   // the SB3 path's per-env scalars, written by the observation pass when bound (pgtg_set_flat_scalars):
-  // the reward as float32, done = terminated | truncated, and truncated-but-not-terminated
+  // the reward as float32, done = terminated | truncated, and truncated-but-not-terminated; with
+  // pgtg_set_flat_cost also the cost of separate_reward_cost as float32
   const double* rew;
   float* rew32;
   uint8_t* dones;
   uint8_t* tonly;
+  const double* cost;
+  float* cost32;
   // the terminal observation's set (final == 2: both passes in one launch)
   const uint8_t* fobs;
   const int32_t* fpos;
@@ -4713,6 +4717,7 @@ __global__ void __launch_bounds__(256, 6) k_flatten(FlatArgs a) {
     a.dones[e] = (uint8_t)((te | tr) != 0);
     a.tonly[e] = (uint8_t)(tr != 0 && te == 0);
     a.rew32[e] = (float)a.rew[e];
+    if (a.cost32) a.cost32[e] = (float)a.cost[e];
   }
 #pragma unroll
   for (int f = 0; f < 2; f++) {  // the observation rows, then the terminal rows
@@ -4965,6 +4970,7 @@ struct pgtg_handle {
   float* flat_rew32 = nullptr;  // pgtg_set_flat_scalars
   uint8_t* flat_dones = nullptr;
   uint8_t* flat_tonly = nullptr;
+  float* flat_cost32 = nullptr;  // pgtg_set_flat_cost (bound only while the three above are)
   int flat_dtype = 0;  // 0 float32, 1 int8
   // episode statistics (pgtg_set_episode_stats): k_episode's arguments.  ep.ret / ep.len / ep.rows are
   // allocated at the first binding and stay; ep.out_ret != nullptr <=> bound
@@ -5789,6 +5795,8 @@ static int launch_flatten(pgtg_handle* h, int mode, uint64_t grid) {
   a.rew32 = final ? nullptr : h->flat_rew32;
   a.dones = final ? nullptr : h->flat_dones;
   a.tonly = final ? nullptr : h->flat_tonly;
+  a.cost = o.cost;
+  a.cost32 = final || !o.cost ? nullptr : h->flat_cost32;  // (outputs rebound without the cost: not written)
   // (float pairs per store: 128 vs 137.7 us per step at 65 536 envs in the pipelined kernel, profiles/r06/s27;
   // in the first row-per-wave kernel they had been slower, 94.7 vs 81.1 us per pass)
   const bool one = a.D <= kFlatU * 64 && a.OB <= 2048;  // (rows of one pass; the bytes fit the LDS window)
@@ -6756,6 +6764,8 @@ int pgtg_set_flat_scalars(pgtg_handle* h, float* reward_f32_dev, uint8_t* dones_
   if (!h) return PGTG_E_INVALID;
   h->flat_rew32 = nullptr;
   h->flat_dones = h->flat_tonly = nullptr;
+  float* const cost32 = h->flat_cost32;
+  h->flat_cost32 = nullptr;  // (the cost row goes with the scalars: unbound with them, kept by a rebinding)
   if (!reward_f32_dev && !dones_dev && !truncated_only_dev) return PGTG_OK;
   if (!reward_f32_dev || !dones_dev || !truncated_only_dev)
     return fail(h, PGTG_E_INVALID, "flat scalars: all three buffers or none");
@@ -6764,6 +6774,20 @@ int pgtg_set_flat_scalars(pgtg_handle* h, float* reward_f32_dev, uint8_t* dones_
   h->flat_rew32 = reward_f32_dev;
   h->flat_dones = dones_dev;
   h->flat_tonly = truncated_only_dev;
+  h->flat_cost32 = cost32;
+  return PGTG_OK;
+}
+
+int pgtg_set_flat_cost(pgtg_handle* h, float* cost_f32_dev) {
+  if (!h) return PGTG_E_INVALID;
+  if (!cost_f32_dev) {
+    h->flat_cost32 = nullptr;
+    return PGTG_OK;
+  }
+  if (!h->hcfg.separate_cost || !h->out.cost)
+    return fail(h, PGTG_E_INVALID, "flat cost needs separate_reward_cost and the cost output");
+  if (!h->flat_rew32) return fail(h, PGTG_E_INVALID, "flat cost: bind the flat scalars first (pgtg_set_flat_scalars)");
+  h->flat_cost32 = cost_f32_dev;
   return PGTG_OK;
 }
 
@@ -6865,6 +6889,52 @@ int pgtg_gae(pgtg_handle* h, const PgtgGae* a) {
   HIPCHK(h, hipSetDevice(h->device));
   if (g.tonly) hipLaunchKernelGGL(k_gae<true>, dim3((unsigned)grid), dim3(kGaeBlock), 0, h->stream, g);
   else hipLaunchKernelGGL(k_gae<false>, dim3((unsigned)grid), dim3(kGaeBlock), 0, h->stream, g);
+  HIPCHK(h, hipGetLastError());
+  return PGTG_OK;
+}
+
+// The cost scan of a rollout and the multiplier's dual ascent (pgtg_cost.h): the handle gives the device,
+// the stream and the error string
+int pgtg_cost_workspace_bytes(uint64_t n, uint64_t* bytes) {
+  if (!bytes || n > (1ull << 40)) return PGTG_E_INVALID;
+  *bytes = (n + kCostBlock - 1) / kCostBlock * sizeof(CostPartial);
+  return PGTG_OK;
+}
+
+int pgtg_cost_scan(pgtg_handle* h, const PgtgCost* a) {
+  if (!h) return PGTG_E_INVALID;
+  if (!a) return fail(h, PGTG_E_INVALID, "pgtg_cost_scan: no arguments");
+  if (a->steps == 0) return fail(h, PGTG_E_INVALID, "pgtg_cost_scan: steps must be at least 1");
+  if (!a->rewards || !a->costs || !a->dones || !a->ep_cost || !a->penalised || !a->lambda || !a->summary || !a->workspace)
+    return fail(h, PGTG_E_INVALID,
+                "pgtg_cost_scan: rewards, costs, dones, ep_cost, penalised, lambda, summary and workspace are required");
+  if ((((uintptr_t)a->ep_cost | (uintptr_t)a->summary | (uintptr_t)a->workspace) & 7u) || ((uintptr_t)a->lambda & 3u))
+    return fail(h, PGTG_E_INVALID, "pgtg_cost_scan: ep_cost, summary and workspace 8-byte aligned, lambda 4-byte aligned");
+  if (!std::isfinite(a->cost_limit) || !std::isfinite(a->lambda_lr))
+    return fail(h, PGTG_E_INVALID, "pgtg_cost_scan: cost_limit and lambda_lr must be finite");
+  if (!(a->lambda_max >= 0.0)) return fail(h, PGTG_E_INVALID, "pgtg_cost_scan: lambda_max must be at least 0");
+  if (a->n == 0) return PGTG_OK;
+  const uint64_t grid = (a->n + kCostBlock - 1) / kCostBlock;
+  if (grid > 0x7fffffffull || a->steps > 0x7fffffffull || a->steps + 1 > UINT64_MAX / 4 / a->n)
+    return fail(h, PGTG_E_UNSUPPORTED, "pgtg_cost_scan: the rollout is too large for one launch");
+  CostArgs c;
+  c.rew = a->rewards;
+  c.cost = a->costs;
+  c.dones = a->dones;
+  c.ep_cost = a->ep_cost;
+  c.pen = a->penalised;
+  c.lambda = a->lambda;
+  c.summary = a->summary;
+  c.rows = reinterpret_cast<CostPartial*>(a->workspace);
+  c.n = a->n;
+  c.steps = a->steps;
+  c.n_rows = grid;
+  c.cost_limit = a->cost_limit;
+  c.lambda_lr = a->lambda_lr;
+  c.lambda_max = a->lambda_max;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_cost_scan, dim3((unsigned)grid), dim3(kCostBlock), 0, h->stream, c);
+  hipLaunchKernelGGL(k_cost_dual, dim3(1), dim3(kCostBlock), 0, h->stream, c);
   HIPCHK(h, hipGetLastError());
   return PGTG_OK;
 }

@@ -26,8 +26,14 @@ which reads obs[t] and writes the action, value and log-probability rows) the lo
                                                                  # k_ppo_reduce into module's .grad, then clip, step, repack
     ro.train_log()                                               # its train/ log (k_ppo_expl_var, k_ppo_log)
 
-While a Rollout records, it owns the handle's flat bindings (set_flat_outputs / set_flat_scalars): bind
-nothing else to them until `close()`.
+On an env with separate_reward_cost, `env.rollout(128, cost_limit=d)` also records the step's cost
+(info["cost"]) into `costs`, and finish() first runs k_cost_scan / k_cost_dual (include/pgtg.h pgtg_cost_scan):
+the cost summed per episode, `penalised_rewards = rewards - lambda * costs` (RCPO, Tessler et al. 2018), which
+k_gae then takes as its rewards, and the multiplier's dual ascent on the mean episode cost against the budget d.
+Rollout k is penalised with the multiplier rollouts 0 .. k-1 produced.  `cost_log()` reads the summary.
+
+While a Rollout records, it owns the handle's flat bindings (set_flat_outputs / set_flat_scalars /
+set_flat_cost): bind nothing else to them until `close()`.
 
 `gae_reference` restates SB3's numpy loop (SB3 is not a dependency; the restatement is the yardstick of the
 tests, as the flatten layout's and the episode statistics' are).
@@ -70,6 +76,82 @@ def gae_reference(rewards, values, dones, truncated_only, terminal_values, last_
         last_gae_lam = delta + gamma * gae_lambda * next_non_terminal * last_gae_lam
         advantages[step] = last_gae_lam
     return advantages, advantages + values
+
+
+COST_BLOCK = 256  # envs per workgroup of k_cost_scan (pgtg_cost.h kCostBlock)
+COST_AHEAD = 8    # rows it keeps in flight ahead of the row it consumes (kCostAhead)
+
+
+def _cost_tree(s, k, m):
+    """cost_block_reduce of pgtg_cost.h over lane values (numpy arrays, any length): 256 lanes per workgroup
+    (the identity in the lanes past the end), each wave of 64 by the shuffle tree -- lane i takes lane i + o for
+    o = 32, 16, .. 1 -- then the four waves in wave order.  Returns one (s, k, m) row per workgroup."""
+    import numpy as np
+    rows = -(-len(s) // COST_BLOCK)
+    pad = rows * COST_BLOCK - len(s)
+    s = np.concatenate([np.asarray(s, np.float64), np.zeros(pad)]).reshape(rows, 4, 64)
+    k = np.concatenate([np.asarray(k, np.uint64), np.zeros(pad, np.uint64)]).reshape(rows, 4, 64)
+    m = np.concatenate([np.asarray(m, np.float64), np.full(pad, -np.inf)]).reshape(rows, 4, 64)
+    o = 32
+    while o:
+        s[..., :o] = s[..., :o] + s[..., o:2 * o]
+        k[..., :o] = k[..., :o] + k[..., o:2 * o]
+        m[..., :o] = np.maximum(m[..., :o], m[..., o:2 * o])
+        o >>= 1
+    rs, rk, rm = s[:, 0, 0].copy(), k[:, 0, 0].copy(), m[:, 0, 0].copy()
+    for w in range(1, 4):
+        rs = rs + s[:, w, 0]
+        rk = rk + k[:, w, 0]
+        rm = np.maximum(rm, m[:, w, 0])
+    return rs, rk, rm
+
+
+def cost_reference(rewards, costs, dones, carry, lam, cost_limit, lambda_lr, lambda_max):
+    """k_cost_scan and k_cost_dual (pgtg_cost.h; include/pgtg.h pgtg_cost_scan) in numpy, statement for
+    statement.  rewards, costs [T, N] float32; dones [T + 1, N] (row t + 1: the episode ended in step t); carry
+    [N] float64, the cost of each env's episode under way; lam the multiplier (float32).  Returns
+    (penalised [T, N] float32, new carry [N] float64, the finished episodes' costs in (env, step) order
+    (float64), summary, next multiplier (numpy float32)); summary has the fields of PgtgCostSummary.  The
+    sums run in the kernels' order: per env in step order, 256 envs per workgroup by _cost_tree, the
+    workgroups' rows by lane t taking rows t, t + 256, ... and the same tree."""
+    import numpy as np
+    rewards = np.asarray(rewards, dtype=np.float32)
+    costs = np.asarray(costs, dtype=np.float32)
+    dones = np.asarray(dones) != 0
+    lam = np.float32(lam)
+    T, N = rewards.shape
+    penalised = np.empty((T, N), np.float32)
+    acc = np.array(carry, dtype=np.float64).reshape(N)  # (a copy)
+    s, k, m = np.zeros(N), np.zeros(N, np.uint64), np.full(N, -np.inf)
+    ends = np.zeros((T, N), bool)
+    sums = np.zeros((T, N))
+    for t in range(T):
+        penalised[t] = rewards[t] - (lam * costs[t]).astype(np.float32)
+        acc = acc + costs[t].astype(np.float64)
+        d = dones[t + 1]
+        s = np.where(d, s + acc, s)
+        k = np.where(d, k + np.uint64(1), k)
+        m = np.where(d, np.maximum(m, acc), m)
+        ends[t], sums[t] = d, acc
+        acc = np.where(d, 0.0, acc)
+    episode_costs = sums.T[ends.T]  # (env, step) order
+    rs, rk, rm = _cost_tree(s, k, m)  # k_cost_scan's rows
+    ls, lk, lm = np.zeros(COST_BLOCK), np.zeros(COST_BLOCK, np.uint64), np.full(COST_BLOCK, -np.inf)
+    for r in range(len(rs)):  # k_cost_dual: lane r % 256 takes the rows in order
+        ln = r % COST_BLOCK
+        ls[ln], lk[ln], lm[ln] = ls[ln] + rs[r], lk[ln] + rk[r], max(lm[ln], rm[r])
+    fs, fk, fm = _cost_tree(ls, lk, lm)
+    total, episodes, worst = float(fs[0]), int(fk[0]), float(fm[0])
+    mean, nxt = 0.0, lam
+    if episodes:
+        mean = total / float(episodes)
+        l = float(lam) + float(lambda_lr) * (mean - float(cost_limit))
+        l = 0.0 if l < 0.0 else l
+        l = float(lambda_max) if l > float(lambda_max) else l
+        nxt = np.float32(l)
+    summary = dict(episodes=episodes, cost_sum=total, cost_mean=mean, cost_max=worst if episodes else 0.0,
+                   lambda_before=lam, lambda_after=nxt)
+    return penalised, acc, episode_costs, summary, nxt
 
 
 PERM_ROUNDS = 6     # Feistel rounds of k_ppo_perm (pgtg_ppo_log.h kPermRounds)
@@ -132,9 +214,15 @@ class Rollout:
       first; rows are padded to 16 bytes, so obs[t] is contiguous and obs as a whole need not be),
       actions [T, N] uint8, rewards [T, N] float32, dones [T+1, N] bool (row t = episode_starts of step t),
       truncated_only [T, N] bool, values / log_probs / terminal_values / advantages / returns [T, N]
-      float32, terminal_obs [N, D] (the last step's terminal observations, valid on its finished envs)."""
+      float32, terminal_obs [N, D] (the last step's terminal observations, valid on its finished envs).
+    With cost_limit (an env with separate_reward_cost; None: nothing of this exists): costs, penalised_rewards
+    [T, N] float32 and ep_cost [N] float64 (the cost of each env's episode under way); lambda_lr, lambda_init and
+    lambda_max are the multiplier's step, start and upper clamp (include/pgtg.h pgtg_cost_scan)."""
 
-    def __init__(self, env, n_steps: int, gamma: float = 0.99, gae_lambda: float = 0.95, obs_dtype=None):
+    def __init__(self, env, n_steps: int, gamma: float = 0.99, gae_lambda: float = 0.95, obs_dtype=None,
+                 cost_limit=None, lambda_lr: float = 0.05, lambda_init: float = 0.0, lambda_max: float = 100.0):
+        import math
+
         import torch
         obs_dtype = torch.int8 if obs_dtype is None else obs_dtype
         if isinstance(obs_dtype, str):
@@ -182,12 +270,31 @@ class Rollout:
         self._train = None      # the last update's statistics buffer, shape and log
         self._stop_word = None  # target_kl's device word
         self._ev_ws = None      # k_ppo_expl_var's workspace
+        self.cost_limit = None if cost_limit is None else float(cost_limit)
+        self._cost_ts = ()
+        if cost_limit is not None:
+            if env.cost is None:
+                raise ValueError("cost_limit needs an env with separate_reward_cost=True (it has no cost channel)")
+            self.lambda_lr, self.lambda_max = float(lambda_lr), float(lambda_max)
+            if not (math.isfinite(self.cost_limit) and math.isfinite(self.lambda_lr) and self.lambda_max >= 0.0
+                    and 0.0 <= float(lambda_init) <= self.lambda_max):
+                raise ValueError("cost_limit and lambda_lr must be finite, and 0 <= lambda_init <= lambda_max")
+            nbytes = C.c_uint64()
+            self._call(env._lib.pgtg_cost_workspace_bytes(N, C.byref(nbytes)))
+            self.costs = torch.zeros((T, N), **f32)
+            self.penalised_rewards = torch.zeros((T, N), **f32)
+            self.ep_cost = torch.zeros(N, dtype=torch.float64, device=dev)
+            self._lambda = torch.full((1,), float(lambda_init), **f32)
+            self._cost_summary = torch.zeros(C.sizeof(_abi.PgtgCostSummary) // 8, dtype=torch.int64, device=dev)
+            self._cost_ws = torch.empty(max(nbytes.value // 8, 1), dtype=torch.float64, device=dev)
+            self._cost_ts = (self.costs, self.penalised_rewards, self.ep_cost, self._lambda, self._cost_summary,
+                             self._cost_ws)
 
     @property
     def nbytes(self) -> int:
         """Device bytes the rollout holds."""
         ts = (self._obs_store, self.terminal_obs, self.actions, self.rewards, self.dones, self.truncated_only,
-              self.values, self.log_probs, self.terminal_values, self.advantages, self.returns)
+              self.values, self.log_probs, self.terminal_values, self.advantages, self.returns) + self._cost_ts
         return sum(t.numel() * t.element_size() for t in ts)
 
     # -- recording -------------------------------------------------------------------------------
@@ -206,6 +313,8 @@ class Rollout:
             env.set_flat_outputs(self.obs[0], self.terminal_obs)
             env.reset(seed=seed)
             self.dones[0].fill_(True)
+            if self.cost_limit is not None:
+                self.ep_cost.zero_()  # (every env starts an episode)
             self._started = True
         else:
             self.obs[0].copy_(self.obs[T])
@@ -245,6 +354,8 @@ class Rollout:
         self._into(self.log_probs[t], log_probs)
         env._bind_flat_ptrs(self.obs[t + 1], self.terminal_obs, self._dtype_code)
         env._bind_flat_scalar_ptrs(self.rewards[t], self.dones[t + 1], self.truncated_only[t])
+        if self.cost_limit is not None:
+            env._bind_flat_cost_ptr(self.costs[t])
         env.step_actions(a)
         self.t = t + 1
         return self.obs[t + 1], self.rewards[t], self.dones[t + 1]
@@ -291,7 +402,9 @@ class Rollout:
         self.finish(policy.value(self.obs[self.n_steps], out=self._last_buf))
 
     def finish(self, last_values) -> None:
-        """advantages and returns of the whole rollout in one launch of k_gae; last_values = V(obs[T])."""
+        """advantages and returns of the whole rollout in one launch of k_gae; last_values = V(obs[T]).
+        With cost_limit, k_cost_scan and k_cost_dual run first and k_gae takes penalised_rewards as its rewards
+        (`rewards` keeps the raw reward)."""
         import torch
         env, T, N = self.env, self.n_steps, self.num_envs
         if self.t != T:
@@ -299,16 +412,54 @@ class Rollout:
         lv = last_values.to(device=self.device, dtype=torch.float32).reshape(N).contiguous()
         self._last_values = lv  # (the launch reads it)
         p = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
-        g = _abi.PgtgGae(n=N, steps=T, gamma=self.gamma, gae_lambda=self.gae_lambda, rewards=p(self.rewards),
+        rewards = self.rewards
+        env._bind_stream()
+        if self.cost_limit is not None:
+            c = _abi.PgtgCost(n=N, steps=T, rewards=p(self.rewards), costs=p(self.costs), dones=p(self.dones),
+                              ep_cost=p(self.ep_cost), penalised=p(self.penalised_rewards), lambda_=p(self._lambda),
+                              cost_limit=self.cost_limit, lambda_lr=self.lambda_lr, lambda_max=self.lambda_max,
+                              summary=p(self._cost_summary), workspace=p(self._cost_ws))
+            self._call(env._lib.pgtg_cost_scan(env._h, C.byref(c)))
+            rewards = self.penalised_rewards
+        g = _abi.PgtgGae(n=N, steps=T, gamma=self.gamma, gae_lambda=self.gae_lambda, rewards=p(rewards),
                          values=p(self.values), dones=p(self.dones), truncated_only=p(self.truncated_only),
                          terminal_values=p(self.terminal_values), last_values=p(lv), advantages=p(self.advantages),
                          returns=p(self.returns))
-        env._bind_stream()
         rc = env._lib.pgtg_gae(env._h, C.byref(g))
         if rc != _abi.PGTG_OK:
             from .vector import _check
             _check(rc, env._h)
         self._finished = True
+
+    # -- the cost channel ----------------------------------------------------------------------
+    def _need_cost(self) -> None:
+        if self.cost_limit is None:
+            raise RuntimeError("the rollout was built without cost_limit")
+
+    def cost_log(self) -> dict:
+        """The cost summary of the last finish(): cost/ep_cost_mean and cost/ep_cost_max over the episodes that
+        ended inside the rollout (cost/episodes of them; 0.0 without any), cost/lambda the multiplier the
+        rollout was penalised with and cost/lambda_next the one the next will be.  One synchronisation."""
+        self._need_cost()
+        if not self._finished:
+            raise RuntimeError("finish() first")
+        s = _abi.PgtgCostSummary.from_buffer_copy(self._cost_summary.cpu().numpy().tobytes())
+        return {"cost/ep_cost_mean": s.cost_mean, "cost/ep_cost_max": s.cost_max, "cost/episodes": int(s.episodes),
+                "cost/lambda": s.lambda_before, "cost/lambda_next": s.lambda_after}
+
+    @property
+    def lagrange_multiplier(self) -> float:
+        """The multiplier the next finish() penalises with (float32).  Reading synchronises; setting writes
+        the device word from the host (checkpoints)."""
+        self._need_cost()
+        return float(self._lambda.item())
+
+    @lagrange_multiplier.setter
+    def lagrange_multiplier(self, value) -> None:
+        self._need_cost()
+        if not 0.0 <= float(value) <= self.lambda_max:
+            raise ValueError("the multiplier lies in [0, lambda_max]")
+        self._lambda.fill_(float(value))
 
     # -- minibatches ---------------------------------------------------------------------------
     def get(self, batch_size: int | None = None, indices=None):
@@ -520,5 +671,5 @@ class Rollout:
         env = self.env
         if env is not None and getattr(env, "_h", None):
             env.set_flat_outputs(None, None)
-            env.set_flat_scalars(None, None, None)
+            env.set_flat_scalars(None, None, None)  # (and with them the cost row)
         self._started = False

@@ -378,6 +378,7 @@ class PGTGVecEnv:
         if all(t is None for t in ts):
             _check(self._lib.pgtg_set_flat_scalars(self._h, None, None, None), self._h)
             self._flat_scalar_refs = ()
+            self._flat_cost_refs = ()  # (the cost row goes with them)
             return
         if any(t is None for t in ts):
             raise ValueError("flat scalars: all three tensors or none")
@@ -390,6 +391,26 @@ class PGTGVecEnv:
         _check(self._lib.pgtg_set_flat_scalars(self._h, C.c_void_p(reward_f32.data_ptr()), C.c_void_p(dones.data_ptr()),
                                                C.c_void_p(truncated_only.data_ptr())), self._h)
         self._flat_scalar_refs = (reward_f32, dones, truncated_only)
+
+    def set_flat_cost(self, cost_f32=None) -> None:
+        """With the flat scalars bound, the same pass also writes the cost of separate_reward_cost as float32
+        into this [N] device tensor (include/pgtg.h pgtg_set_flat_cost).  None unbinds, as does
+        set_flat_scalars(None, None, None).  ValueError on an env without the cost channel and before the
+        scalars are bound."""
+        import torch
+        if cost_f32 is None:
+            _check(self._lib.pgtg_set_flat_cost(self._h, None), self._h)
+            self._flat_cost_refs = ()
+            return
+        if (cost_f32.dtype != torch.float32 or tuple(cost_f32.shape) != (self.num_envs,) or not cost_f32.is_contiguous()
+                or cost_f32.device != self.device):
+            raise ValueError(f"flat cost: a contiguous [{self.num_envs}] float32 tensor on {self.device}")
+        self._bind_flat_cost_ptr(cost_f32)
+
+    def _bind_flat_cost_ptr(self, cost_f32) -> None:
+        """Rebind a cost row of the shape and dtype set_flat_cost checks (the per-step path of Rollout)."""
+        _check(self._lib.pgtg_set_flat_cost(self._h, C.c_void_p(cost_f32.data_ptr())), self._h)
+        self._flat_cost_refs = (cost_f32,)
 
     def _bind_flat_ptrs(self, flat, final_flat, dtype_code: int) -> None:
         """Rebind flat rows already checked by set_flat_outputs (same shape and dtype): the per-step
@@ -578,13 +599,14 @@ class PGTGVecEnv:
         snap.load(self, torch.arange(src.numel(), device=self.device), dst, observe=observe, check=check)
 
     # -- PPO rollout buffer on the device (SB3's RolloutBuffer, pgtg/train.py:61-74) -------------------
-    def rollout(self, n_steps: int, gamma: float = 0.99, gae_lambda: float = 0.95, obs_dtype=None):
+    def rollout(self, n_steps: int, gamma: float = 0.99, gae_lambda: float = 0.95, obs_dtype=None, **cost):
         """A Rollout (pgtg_amd/rollout.py) of n_steps steps of this batch: the steps record themselves into
         its rows, finish() is the HIP kernel k_gae.  obs_dtype: torch.int8 (default) or torch.float32.
         Needs autoreset=True and a flattenable observation (ValueError otherwise).  While it records, the
-        Rollout owns this handle's flat bindings (set_flat_outputs / set_flat_scalars)."""
+        Rollout owns this handle's flat bindings (set_flat_outputs / set_flat_scalars / set_flat_cost).
+        cost: Rollout's cost_limit, lambda_lr, lambda_init, lambda_max (an env with separate_reward_cost)."""
         from .rollout import Rollout
-        return Rollout(self, n_steps, gamma, gae_lambda, obs_dtype)
+        return Rollout(self, n_steps, gamma, gae_lambda, obs_dtype, **cost)
 
     # -- policy evaluation on the device (ModularEvaluator.evaluate, pgtg/evaluator.py:284-339) --------
     def evaluation(self, n_episodes: int, gamma: float = 0.99):
@@ -599,7 +621,7 @@ class PGTGVecEnv:
         """Every tensor a step launch writes: the outputs and whatever else is bound."""
         ts = [self.obs_map, self.position, self.velocity, self.reward, self.terminated, self.truncated, self.braking,
               self.cost, self.nsd, self.final_map, self.final_position, self.final_velocity, self.final_nsd]
-        for refs in ("_flat_refs", "_flat_scalar_refs", "_episode_refs"):
+        for refs in ("_flat_refs", "_flat_scalar_refs", "_flat_cost_refs", "_episode_refs"):
             ts += list(getattr(self, refs, ()) or ())
         return [t for t in ts if t is not None]
 
