@@ -20,6 +20,8 @@
  *                        PPO the reference's caller trains                 pgtg/train.py:61-74
  *   pgtg_set_flat_cost / pgtg_cost_scan <- info["cost"] of separate_reward_cost through the rollout, and
  *                        a Lagrange multiplier on it (new past the step)  environment.py:1130-1276
+ *   pgtg_reward_norm  <- (new, no reference function) the reward half of the VecNormalize an SB3 user
+ *                        wraps the env in, for rewards the size of train.py's   pgtg/train.py:21-38
  *   pgtg_policy / pgtg_policy_pack <- (new, no reference function) the acting forward pass of the
  *                        MlpPolicy that PPO collects with                  pgtg/train.py:61-74
  *   pgtg_eval_step / pgtg_eval_summary <- ModularEvaluator.evaluate for the batch, with the per-env
@@ -413,6 +415,43 @@ typedef struct {
 } PgtgCost;
 int pgtg_cost_workspace_bytes(uint64_t n, uint64_t* bytes);
 int pgtg_cost_scan(pgtg_handle* h, const PgtgCost* a);
+/* Running return normalisation of the reward of a device-resident rollout of N envs and T steps (new; no
+ * reference function: SB3's VecNormalize(norm_reward=True), reward half, which a user of the reference wraps the
+ * env in).  In fp64, no fused multiply-add, per step t = 0 .. T-1 in order, ret = returns, (mean, var, count) = rms:
+ *   ret[e] = ret[e] * gamma + (double)rewards[t][e]
+ *   (nb, mb, vb) = the count, mean and population variance of ret over the N envs
+ *   delta = mb - mean;  tot = count + nb;  mean' = mean + delta * nb / tot
+ *   var' = (var * count + vb * nb + delta * delta * count * nb / tot) / tot;  count' = tot
+ *   row_var[t] = var';  normalised[t][e] = (float)min(max((double)rewards[t][e] / sqrt(var' + epsilon), -clip), clip)
+ *   dones[t+1][e] != 0:  ret[e] = 0
+ * (RunningMeanStd.update_from_moments; step t is normalised with statistics that include step t, as SB3 does).
+ * Four launches: k_ret_scan (one lane per env; each wave of 64 envs writes the (n, mean, M2) of its returns per
+ * step into the workspace), k_ret_stats twice (one workgroup per step merges that step's partials; then one lane
+ * walks the steps) and k_ret_apply (elementwise).  The moments are merged pairwise and count-aware (Chan et al.:
+ * n = na + nb; d = mb - ma; mean = ma + d * (nb / n); M2 = M2a + M2b + d * d * (na * nb / n); an empty operand
+ * returns the other), each wave by a shuffle tree, a step's waves by lane l taking partials l, l + 256, ... and the
+ * same tree: every order is a function of N and T alone, so the same arrays give the same bits on any device.
+ * training == 0: returns, rms and row_var are left as they are, and k_ret_apply alone runs, every row divided
+ * by sqrt(rms[1] + epsilon).  All pointers are device pointers; returns, rms, row_var and workspace
+ * (pgtg_reward_norm_workspace_bytes(n, steps) bytes, contents irrelevant) 8-byte aligned.  The handle is used
+ * for its device, stream and error string only.  steps == 0, a NULL or misaligned pointer, a negative or
+ * non-finite epsilon or clip, gamma outside [0, 1] or NaN: PGTG_E_INVALID; a rollout beyond one launch
+ * (pgtg_gae's limits): PGTG_E_UNSUPPORTED; each with a message, nothing launched.  n == 0 is a no-op.
+ * Asynchronous on the handle's stream. */
+typedef struct {
+  uint64_t n, steps;
+  double gamma, epsilon, clip;
+  int32_t training;           /* 0: the statistics and returns are frozen */
+  const float*   rewards;     /* [T][N] */
+  const uint8_t* dones;       /* [T+1][N]: row t+1 = the episode ended in step t */
+  double* returns;            /* [N] the discounted return of the episode under way (in/out) */
+  double* rms;                /* [3] mean, var, count of the returns seen so far (in/out) */
+  double* row_var;            /* [T] out: var after step t */
+  float*  normalised;         /* [T][N] out */
+  void* workspace;
+} PgtgRewardNorm;
+int pgtg_reward_norm_workspace_bytes(uint64_t n, uint64_t steps, uint64_t* bytes);
+int pgtg_reward_norm(pgtg_handle* h, const PgtgRewardNorm* a);
 /* The acting forward pass of SB3's MlpPolicy over int8 flat rows (new; no reference function: it replaces
  * ActorCriticPolicy.forward / predict_values of the PPO("MlpPolicy") of pgtg/train.py:61-74 inside
  * collect_rollouts).  Separate pi / vf towers, 64-64, tanh, 9 actions; float32 throughout.  Per env e,

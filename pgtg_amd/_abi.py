@@ -35,6 +35,7 @@ EXPORTED = [
     "pgtg_set_to_state", "pgtg_car_digest", "pgtg_get_queue_maps", "pgtg_get_step_launches", "pgtg_set_block_shares", "pgtg_get_block_shares", "pgtg_get_queue_overflow", "pgtg_set_flat_outputs", "pgtg_set_flat_scalars",
     "pgtg_set_episode_stats", "pgtg_episode_summary", "pgtg_gae", "pgtg_flatten",
     "pgtg_set_flat_cost", "pgtg_cost_workspace_bytes", "pgtg_cost_scan",
+    "pgtg_reward_norm_workspace_bytes", "pgtg_reward_norm",
     "pgtg_eval_step", "pgtg_eval_summary", "pgtg_eval_workspace_bytes",
     "pgtg_policy", "pgtg_policy_pack", "pgtg_policy_packed_bytes", "pgtg_policy_chunk",
     "pgtg_ppo_workspace_bytes", "pgtg_ppo_grad",
@@ -121,7 +122,13 @@ class PgtgCost(C.Structure):
         ("summary", C.c_void_p), ("workspace", C.c_void_p)]
 
 
-EVAL_STATE_FIELDS = ("ret", "disc", "g", "len", "cnt")
+class PgtgRewardNorm(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("steps", C.c_uint64), ("gamma", C.c_double), ("epsilon", C.c_double),
+                ("clip", C.c_double), ("training", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("rewards", "dones", "returns", "rms", "row_var", "normalised", "workspace")]
+
+
+EVAL_STATE_FIELDS =("ret", "disc", "g", "len", "cnt")
 EVAL_RECORD_FIELDS = ("rec_return", "rec_discounted", "rec_length", "rec_last_reward", "rec_end_step", "rec_flags")
 
 
@@ -244,6 +251,8 @@ def lib():
         "pgtg_set_flat_cost": ([vp, vp], C.c_int),
         "pgtg_cost_workspace_bytes": ([u64, C.POINTER(u64)], C.c_int),
         "pgtg_cost_scan": ([vp, C.POINTER(PgtgCost)], C.c_int),
+        "pgtg_reward_norm_workspace_bytes": ([u64, u64, C.POINTER(u64)], C.c_int),
+        "pgtg_reward_norm": ([vp, C.POINTER(PgtgRewardNorm)], C.c_int),
         "pgtg_eval_step": ([vp, C.POINTER(PgtgEval)], C.c_int),
         "pgtg_eval_summary": ([vp, C.POINTER(PgtgEval), vp, vp], C.c_int),
         "pgtg_eval_workspace_bytes": ([u64, u64, C.POINTER(u64)], C.c_int),

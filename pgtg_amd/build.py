@@ -12,6 +12,7 @@ DEPS = [SRC, os.path.join(PKG, "csrc", "pgtg_device.h"), os.path.join(PKG, "csrc
         os.path.join(PKG, "csrc", "pgtg_episode.h"), os.path.join(PKG, "csrc", "pgtg_eval.h"),
         os.path.join(PKG, "csrc", "pgtg_snapshot.h"),
         os.path.join(PKG, "csrc", "pgtg_rollout.h"), os.path.join(PKG, "csrc", "pgtg_cost.h"),
+        os.path.join(PKG, "csrc", "pgtg_norm.h"),
         os.path.join(PKG, "csrc", "pgtg_policy.h"),
         os.path.join(PKG, "csrc", "pgtg_ppo.h"), os.path.join(PKG, "csrc", "pgtg_ppo_step.h"),
         os.path.join(PKG, "csrc", "pgtg_ppo_log.h"), os.path.join(PKG, "csrc", "pgtg_shares.h"),

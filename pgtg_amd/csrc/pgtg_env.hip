@@ -30,6 +30,7 @@
 #include "pgtg_eval.h"
 #include "pgtg_rollout.h"
 #include "pgtg_cost.h"
+#include "pgtg_norm.h"
 #include "pgtg_policy.h"
 #include "pgtg_ppo.h"
 #include "pgtg_ppo_step.h"
@@ -6935,6 +6936,67 @@ int pgtg_cost_scan(pgtg_handle* h, const PgtgCost* a) {
   HIPCHK(h, hipSetDevice(h->device));
   hipLaunchKernelGGL(k_cost_scan, dim3((unsigned)grid), dim3(kCostBlock), 0, h->stream, c);
   hipLaunchKernelGGL(k_cost_dual, dim3(1), dim3(kCostBlock), 0, h->stream, c);
+  HIPCHK(h, hipGetLastError());
+  return PGTG_OK;
+}
+
+// Running return normalisation of a rollout's reward (pgtg_norm.h): the handle gives the device, the stream
+// and the error string.  What bounds a rollout for the launch geometry; pgtg_gae's limits.
+static bool norm_too_large(uint64_t n, uint64_t steps) {
+  return (n + kNormBlock - 1) / kNormBlock > 0x7fffffffull || steps > 0x7fffffffull || steps + 1 > UINT64_MAX / 4 / n;
+}
+
+int pgtg_reward_norm_workspace_bytes(uint64_t n, uint64_t steps, uint64_t* bytes) {
+  if (!bytes || n > (1ull << 40) || steps > 0x7fffffffull) return PGTG_E_INVALID;
+  if (n && steps && norm_too_large(n, steps)) return PGTG_E_UNSUPPORTED;
+  // the waves' partials of every step, then every step's merged moments
+  *bytes = steps * ((n + kNormPartial - 1) / kNormPartial + (n ? 1 : 0)) * sizeof(RetPartial);
+  return PGTG_OK;
+}
+
+int pgtg_reward_norm(pgtg_handle* h, const PgtgRewardNorm* a) {
+  if (!h) return PGTG_E_INVALID;
+  if (!a) return fail(h, PGTG_E_INVALID, "pgtg_reward_norm: no arguments");
+  if (a->steps == 0) return fail(h, PGTG_E_INVALID, "pgtg_reward_norm: steps must be at least 1");
+  if (!a->rewards || !a->dones || !a->returns || !a->rms || !a->row_var || !a->normalised || !a->workspace)
+    return fail(h, PGTG_E_INVALID,
+                "pgtg_reward_norm: rewards, dones, returns, rms, row_var, normalised and workspace are required");
+  if (((uintptr_t)a->returns | (uintptr_t)a->rms | (uintptr_t)a->row_var | (uintptr_t)a->workspace) & 7u)
+    return fail(h, PGTG_E_INVALID, "pgtg_reward_norm: returns, rms, row_var and workspace 8-byte aligned");
+  if ((uintptr_t)a->rewards & 3u || (uintptr_t)a->normalised & 3u)
+    return fail(h, PGTG_E_INVALID, "pgtg_reward_norm: rewards and normalised 4-byte aligned");
+  if (!std::isfinite(a->epsilon) || a->epsilon < 0.0 || !std::isfinite(a->clip) || a->clip < 0.0)
+    return fail(h, PGTG_E_INVALID, "pgtg_reward_norm: epsilon and clip must be finite and at least 0");
+  if (!(a->gamma >= 0.0 && a->gamma <= 1.0)) return fail(h, PGTG_E_INVALID, "pgtg_reward_norm: gamma must be in [0, 1]");
+  if (a->n == 0) return PGTG_OK;
+  if (norm_too_large(a->n, a->steps))
+    return fail(h, PGTG_E_UNSUPPORTED, "pgtg_reward_norm: the rollout is too large for one launch");
+  NormArgs c;
+  c.rew = a->rewards;
+  c.dones = a->dones;
+  c.ret = a->returns;
+  c.rms = a->rms;
+  c.row_var = a->row_var;
+  c.out = a->normalised;
+  c.n = a->n;
+  c.steps = a->steps;
+  c.n_part = (a->n + kNormPartial - 1) / kNormPartial;
+  c.rows = reinterpret_cast<RetPartial*>(a->workspace);
+  c.batch = c.rows + a->steps * c.n_part;
+  c.gamma = a->gamma;
+  c.epsilon = a->epsilon;
+  c.clip = a->clip;
+  c.training = a->training != 0;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (c.training) {
+    const unsigned grid = (unsigned)((a->n + kNormBlock - 1) / kNormBlock);
+    hipLaunchKernelGGL(k_ret_scan, dim3(grid), dim3(kNormBlock), 0, h->stream, c);
+    hipLaunchKernelGGL(k_ret_stats<false>, dim3((unsigned)a->steps), dim3(kNormBlock), 0, h->stream, c);
+    hipLaunchKernelGGL(k_ret_stats<true>, dim3(1), dim3(kNormBlock), 0, h->stream, c);
+  }
+  const uint64_t per = (uint64_t)kNormBlock * kNormApplyCols;
+  const dim3 grid((unsigned)((a->n + per - 1) / per), (unsigned)std::min<uint64_t>(a->steps, 65535));
+  hipLaunchKernelGGL(k_ret_apply, grid, dim3(kNormBlock), 0, h->stream, c);
   HIPCHK(h, hipGetLastError());
   return PGTG_OK;
 }

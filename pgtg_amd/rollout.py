@@ -32,6 +32,14 @@ the cost summed per episode, `penalised_rewards = rewards - lambda * costs` (RCP
 k_gae then takes as its rewards, and the multiplier's dual ascent on the mean episode cost against the budget d.
 Rollout k is penalised with the multiplier rollouts 0 .. k-1 produced.  `cost_log()` reads the summary.
 
+`env.rollout(128, norm_reward=True)` is SB3's `VecNormalize(norm_reward=True)` around the env, reward half:
+finish() first runs k_ret_scan / k_ret_stats / k_ret_apply (include/pgtg.h pgtg_reward_norm), which carry each env's
+discounted return and the running mean, variance and count of those returns across rollouts and write
+`normalised_rewards = clip(rewards / sqrt(var + epsilon), +-clip_reward)`; the cost scan and k_gae then take those
+(`rewards` keeps the raw reward).  `reward_norm_state()` / `load_reward_norm_state()` are its checkpoint,
+`norm_training = False` freezes the statistics, `norm_log()` reads them.  `reward_norm_reference` restates the
+kernels in numpy.  Observations are not normalised: the rows are int8 flags.
+
 While a Rollout records, it owns the handle's flat bindings (set_flat_outputs / set_flat_scalars /
 set_flat_cost): bind nothing else to them until `close()`.
 
@@ -154,6 +162,106 @@ def cost_reference(rewards, costs, dones, carry, lam, cost_limit, lambda_lr, lam
     return penalised, acc, episode_costs, summary, nxt
 
 
+NORM_BLOCK = 256   # lanes per workgroup of k_ret_scan and k_ret_stats (pgtg_norm.h kNormBlock)
+NORM_PARTIAL = 64  # envs per partial of a step: one wave (kNormPartial)
+NORM_AHEAD = 8     # rows k_ret_scan keeps in flight, and steps whose trees it reduces side by side (kNormAhead)
+NORM_RMS_INIT = (0.0, 1.0, 1e-4)  # RunningMeanStd's (mean, var, count) before any sample
+
+
+def _ret_merge(a, b):
+    """ret_merge of pgtg_norm.h on (n, mean, m2) triples of equal-shaped float64 arrays: Chan's count-aware merge,
+    a then b, an empty operand returning the other unchanged."""
+    import numpy as np
+    (na, ma, sa), (nb, mb, sb) = a, b
+    with np.errstate(divide="ignore", invalid="ignore"):
+        n = na + nb
+        d = mb - ma
+        mean = ma + d * (nb / n)
+        m2 = sa + sb + d * d * (na * nb / n)
+    ea, eb = na == 0, nb == 0
+    pick = lambda x, xa, xb: np.where(eb, xa, np.where(ea, xb, x))  # noqa: E731
+    return pick(n, na, nb), pick(mean, ma, mb), pick(m2, sa, sb)
+
+
+def _ret_tree(n, mean, m2):
+    """The shuffle tree over the last axis (64 lanes): lane i merges lane i + o into itself for o = 32, 16, .. 1;
+    returns lane 0's triple."""
+    n, mean, m2 = n.copy(), mean.copy(), m2.copy()
+    o = 32
+    while o:
+        r = _ret_merge((n[..., :o], mean[..., :o], m2[..., :o]), (n[..., o:2 * o], mean[..., o:2 * o], m2[..., o:2 * o]))
+        n[..., :o], mean[..., :o], m2[..., :o] = r
+        o >>= 1
+    return n[..., 0], mean[..., 0], m2[..., 0]
+
+
+def _ret_pad(x, width):
+    """x [T, K] padded with zeros (empty partials) to a multiple of `width` columns, as [T, K / width, width]."""
+    import numpy as np
+    T, K = x.shape
+    rows = -(-K // width)
+    return np.concatenate([x, np.zeros((T, rows * width - K))], axis=1).reshape(T, rows, width)
+
+
+def reward_norm_reference(rewards, dones, ret, rms, gamma, epsilon=1e-8, clip=10.0, training=True):
+    """k_ret_scan, k_ret_stats and k_ret_apply (pgtg_norm.h; include/pgtg.h pgtg_reward_norm) in numpy float64,
+    statement for statement and merge for merge: the reward half of SB3's VecNormalize.  rewards [T, N] float32;
+    dones [T + 1, N] (row t + 1: the episode ended in step t); ret [N] float64, the discounted return of each
+    env's episode under way; rms = (mean, var, count) of the returns seen so far.  Returns (normalised [T, N]
+    float32, new ret [N], new rms float64 [3], row_var float64 [T]: the variance row t was divided with).
+    training=False: ret and rms come back as they were and every row is divided by sqrt(rms[1] + epsilon).
+    The moments of a step are merged in the kernels' order: 64 envs per wave by _ret_tree, the waves' partials
+    by lane l taking partials l, l + 256, ... in order, those 256 by the same tree per wave and the four waves
+    in wave order; then update_from_moments step by step."""
+    import numpy as np
+    rewards = np.asarray(rewards, dtype=np.float32)
+    dones = np.asarray(dones) != 0
+    T, N = rewards.shape
+    gamma, epsilon, clip = float(gamma), float(epsilon), float(clip)
+    ret = np.array(ret, dtype=np.float64).reshape(N)  # (a copy)
+    mean, var, count = (float(x) for x in np.asarray(rms, dtype=np.float64).reshape(3))
+    r64 = rewards.astype(np.float64)
+    if training:
+        # k_ret_scan: the returns of every step, then each wave's tree
+        rets = np.empty((T, N))
+        for t in range(T):
+            ret = ret * gamma + r64[t]
+            rets[t] = ret
+            ret = np.where(dones[t + 1], 0.0, ret)
+        leaves_n = _ret_pad(np.ones((T, N)), NORM_PARTIAL)
+        pn, pm, ps = _ret_tree(leaves_n, _ret_pad(rets, NORM_PARTIAL), np.zeros_like(leaves_n))  # [T, W]
+        # k_ret_stats, the merge: lane l takes the partials l, l + 256, ... in order
+        ln, lm, ls = (_ret_pad(x, NORM_BLOCK) for x in (pn, pm, ps))  # [T, rounds, 256]
+        acc = tuple(np.zeros((T, NORM_BLOCK)) for _ in range(3))
+        for k in range(ln.shape[1]):
+            acc = _ret_merge(acc, (ln[:, k], lm[:, k], ls[:, k]))
+        wn, wm, ws = _ret_tree(*(x.reshape(T, NORM_BLOCK // 64, 64) for x in acc))  # [T, 4]
+        b = (wn[:, 0], wm[:, 0], ws[:, 0])
+        for w in range(1, NORM_BLOCK // 64):
+            b = _ret_merge(b, (wn[:, w], wm[:, w], ws[:, w]))
+        # k_ret_stats, the walk: RunningMeanStd.update_from_moments
+        row_var = np.empty(T)
+        for t in range(T):
+            nb, mb = float(b[0][t]), float(b[1][t])
+            vb = float(b[2][t]) / nb
+            delta = mb - mean
+            tot = count + nb
+            nxt = mean + delta * nb / tot
+            var = (var * count + vb * nb + delta * delta * count * nb / tot) / tot
+            mean, count = nxt, tot
+            row_var[t] = var
+    else:
+        row_var = np.full(T, var)
+    # k_ret_apply
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = r64 / np.sqrt(row_var + epsilon)[:, None]
+    q = np.where(q < -clip, -clip, q)
+    q = np.where(q > clip, clip, q)
+    with np.errstate(over="ignore"):
+        normalised = q.astype(np.float32)
+    return normalised, ret, np.array([mean, var, count]), row_var
+
+
 PERM_ROUNDS = 6     # Feistel rounds of k_ppo_perm (pgtg_ppo_log.h kPermRounds)
 PERM_WALK_CAP = 64  # cycle-walk steps of an element at most (kPermWalkCap)
 
@@ -217,10 +325,15 @@ class Rollout:
       float32, terminal_obs [N, D] (the last step's terminal observations, valid on its finished envs).
     With cost_limit (an env with separate_reward_cost; None: nothing of this exists): costs, penalised_rewards
     [T, N] float32 and ep_cost [N] float64 (the cost of each env's episode under way); lambda_lr, lambda_init and
-    lambda_max are the multiplier's step, start and upper clamp (include/pgtg.h pgtg_cost_scan)."""
+    lambda_max are the multiplier's step, start and upper clamp (include/pgtg.h pgtg_cost_scan).
+    With norm_reward (False: nothing of this exists): normalised_rewards [T, N] float32, ret [N] float64 (the
+    discounted return of each env's episode under way), ret_rms [3] float64 (mean, var, count of the returns seen
+    so far) and row_var [T] float64; clip_reward, norm_epsilon and norm_gamma (None: gamma) are VecNormalize's
+    clip_reward, epsilon and gamma (include/pgtg.h pgtg_reward_norm); norm_training (True) as its `training`."""
 
     def __init__(self, env, n_steps: int, gamma: float = 0.99, gae_lambda: float = 0.95, obs_dtype=None,
-                 cost_limit=None, lambda_lr: float = 0.05, lambda_init: float = 0.0, lambda_max: float = 100.0):
+                 cost_limit=None, lambda_lr: float = 0.05, lambda_init: float = 0.0, lambda_max: float = 100.0,
+                 norm_reward: bool = False, clip_reward: float = 10.0, norm_epsilon: float = 1e-8, norm_gamma=None):
         import math
 
         import torch
@@ -289,12 +402,30 @@ class Rollout:
             self._cost_ws = torch.empty(max(nbytes.value // 8, 1), dtype=torch.float64, device=dev)
             self._cost_ts = (self.costs, self.penalised_rewards, self.ep_cost, self._lambda, self._cost_summary,
                              self._cost_ws)
+        self.norm_reward = bool(norm_reward)
+        self._norm_ts = ()
+        if self.norm_reward:
+            self.clip_reward, self.norm_epsilon = float(clip_reward), float(norm_epsilon)
+            self.norm_gamma = self.gamma if norm_gamma is None else float(norm_gamma)
+            if not (math.isfinite(self.clip_reward) and self.clip_reward >= 0.0 and math.isfinite(self.norm_epsilon)
+                    and self.norm_epsilon >= 0.0 and 0.0 <= self.norm_gamma <= 1.0):
+                raise ValueError("clip_reward and norm_epsilon must be finite and at least 0, norm_gamma in [0, 1]")
+            nbytes = C.c_uint64()
+            self._call(env._lib.pgtg_reward_norm_workspace_bytes(N, T, C.byref(nbytes)))
+            self.norm_training = True
+            self.normalised_rewards = torch.zeros((T, N), **f32)
+            self.ret = torch.zeros(N, dtype=torch.float64, device=dev)
+            self.ret_rms = torch.tensor(NORM_RMS_INIT, dtype=torch.float64, device=dev)
+            self.row_var = torch.zeros(T, dtype=torch.float64, device=dev)
+            self._norm_ws = torch.empty(max(nbytes.value // 8, 1), dtype=torch.float64, device=dev)
+            self._norm_ts = (self.normalised_rewards, self.ret, self.ret_rms, self.row_var, self._norm_ws)
 
     @property
     def nbytes(self) -> int:
         """Device bytes the rollout holds."""
         ts = (self._obs_store, self.terminal_obs, self.actions, self.rewards, self.dones, self.truncated_only,
               self.values, self.log_probs, self.terminal_values, self.advantages, self.returns) + self._cost_ts
+        ts += self._norm_ts
         return sum(t.numel() * t.element_size() for t in ts)
 
     # -- recording -------------------------------------------------------------------------------
@@ -315,6 +446,8 @@ class Rollout:
             self.dones[0].fill_(True)
             if self.cost_limit is not None:
                 self.ep_cost.zero_()  # (every env starts an episode)
+            if self.norm_reward:
+                self.ret.zero_()  # (VecNormalize.reset: the returns restart, the statistics stay)
             self._started = True
         else:
             self.obs[0].copy_(self.obs[T])
@@ -404,7 +537,9 @@ class Rollout:
     def finish(self, last_values) -> None:
         """advantages and returns of the whole rollout in one launch of k_gae; last_values = V(obs[T]).
         With cost_limit, k_cost_scan and k_cost_dual run first and k_gae takes penalised_rewards as its rewards
-        (`rewards` keeps the raw reward)."""
+        (`rewards` keeps the raw reward).  With norm_reward, k_ret_scan, k_ret_stats and k_ret_apply run before
+        either (only k_ret_apply when norm_training is False), and what follows takes normalised_rewards: the
+        normalisation wraps the env, so the penalty and the advantages act on what the agent sees."""
         import torch
         env, T, N = self.env, self.n_steps, self.num_envs
         if self.t != T:
@@ -414,8 +549,15 @@ class Rollout:
         p = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
         rewards = self.rewards
         env._bind_stream()
+        if self.norm_reward:
+            r = _abi.PgtgRewardNorm(n=N, steps=T, gamma=self.norm_gamma, epsilon=self.norm_epsilon, clip=self.clip_reward,
+                                    training=int(bool(self.norm_training)), rewards=p(rewards), dones=p(self.dones),
+                                    returns=p(self.ret), rms=p(self.ret_rms), row_var=p(self.row_var),
+                                    normalised=p(self.normalised_rewards), workspace=p(self._norm_ws))
+            self._call(env._lib.pgtg_reward_norm(env._h, C.byref(r)))
+            rewards = self.normalised_rewards
         if self.cost_limit is not None:
-            c = _abi.PgtgCost(n=N, steps=T, rewards=p(self.rewards), costs=p(self.costs), dones=p(self.dones),
+            c = _abi.PgtgCost(n=N, steps=T, rewards=p(rewards), costs=p(self.costs), dones=p(self.dones),
                               ep_cost=p(self.ep_cost), penalised=p(self.penalised_rewards), lambda_=p(self._lambda),
                               cost_limit=self.cost_limit, lambda_lr=self.lambda_lr, lambda_max=self.lambda_max,
                               summary=p(self._cost_summary), workspace=p(self._cost_ws))
@@ -460,6 +602,36 @@ class Rollout:
         if not 0.0 <= float(value) <= self.lambda_max:
             raise ValueError("the multiplier lies in [0, lambda_max]")
         self._lambda.fill_(float(value))
+
+    # -- reward normalisation ------------------------------------------------------------------
+    def _need_norm(self) -> None:
+        if not self.norm_reward:
+            raise RuntimeError("the rollout was built without norm_reward")
+
+    def reward_norm_state(self) -> dict:
+        """Host copies of the running statistics and the returns under way: {"mean", "var", "count"} (floats)
+        and "ret" (float64 numpy [N]) -- what VecNormalize.save keeps of the reward half.  Synchronises."""
+        self._need_norm()
+        mean, var, count = self.ret_rms.cpu().tolist()
+        return {"mean": mean, "var": var, "count": count, "ret": self.ret.cpu().numpy().copy()}
+
+    def load_reward_norm_state(self, state: dict) -> None:
+        """Restore what reward_norm_state() returned (a checkpoint's): the device words are written from the host."""
+        import numpy as np
+        import torch
+        self._need_norm()
+        ret = np.asarray(state["ret"], dtype=np.float64)
+        if ret.shape != (self.num_envs,):
+            raise ValueError(f"ret: a float64 array of shape ({self.num_envs},)")
+        rms = [float(state["mean"]), float(state["var"]), float(state["count"])]
+        self.ret_rms.copy_(torch.tensor(rms, dtype=torch.float64))
+        self.ret.copy_(torch.from_numpy(np.ascontiguousarray(ret)))
+
+    def norm_log(self) -> dict:
+        """The running statistics of the discounted return as they stand.  One synchronisation."""
+        self._need_norm()
+        mean, var, count = self.ret_rms.cpu().tolist()
+        return {"norm/ret_mean": mean, "norm/ret_var": var, "norm/count": count}
 
     # -- minibatches ---------------------------------------------------------------------------
     def get(self, batch_size: int | None = None, indices=None):

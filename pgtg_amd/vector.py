@@ -599,14 +599,20 @@ class PGTGVecEnv:
         snap.load(self, torch.arange(src.numel(), device=self.device), dst, observe=observe, check=check)
 
     # -- PPO rollout buffer on the device (SB3's RolloutBuffer, pgtg/train.py:61-74) -------------------
-    def rollout(self, n_steps: int, gamma: float = 0.99, gae_lambda: float = 0.95, obs_dtype=None, **cost):
+    def rollout(self, n_steps: int, gamma: float = 0.99, gae_lambda: float = 0.95, obs_dtype=None, *,
+                norm_reward: bool = False, clip_reward: float = 10.0, norm_epsilon: float = 1e-8, norm_gamma=None,
+                **cost):
         """A Rollout (pgtg_amd/rollout.py) of n_steps steps of this batch: the steps record themselves into
         its rows, finish() is the HIP kernel k_gae.  obs_dtype: torch.int8 (default) or torch.float32.
         Needs autoreset=True and a flattenable observation (ValueError otherwise).  While it records, the
         Rollout owns this handle's flat bindings (set_flat_outputs / set_flat_scalars / set_flat_cost).
-        cost: Rollout's cost_limit, lambda_lr, lambda_init, lambda_max (an env with separate_reward_cost)."""
+        cost: Rollout's cost_limit, lambda_lr, lambda_init, lambda_max (an env with separate_reward_cost).
+        norm_reward: SB3's VecNormalize(norm_reward=True) inside finish() -- the running variance of the
+        discounted return scales the rewards k_gae sees (k_ret_scan, k_ret_stats, k_ret_apply); clip_reward,
+        norm_epsilon and norm_gamma (None: gamma) are its clip_reward, epsilon and gamma."""
         from .rollout import Rollout
-        return Rollout(self, n_steps, gamma, gae_lambda, obs_dtype, **cost)
+        return Rollout(self, n_steps, gamma, gae_lambda, obs_dtype, norm_reward=norm_reward, clip_reward=clip_reward,
+                       norm_epsilon=norm_epsilon, norm_gamma=norm_gamma, **cost)
 
     # -- policy evaluation on the device (ModularEvaluator.evaluate, pgtg/evaluator.py:284-339) --------
     def evaluation(self, n_episodes: int, gamma: float = 0.99):
