@@ -1,6 +1,7 @@
 """Diagnostic: per-phase wave cycles of k_env from the -DPGTG_STAMPS build (not the product).
 
-Build: hipcc <pgtg_amd.build.FLAGS> -DPGTG_STAMPS -o pgtg_amd/libpgtg_hip_stamps.so pgtg_amd/csrc/pgtg_env.hip
+Build: python -m pgtg_amd.build --tools=stamps  (pgtg_env.hip with -DPGTG_STAMPS, linked with the train object into
+pgtg_amd/libpgtg_hip_stamps.so)
 Usage: python tools/stamps.py [cfg2|cfg5|cfg3 ...]
 PGTG_STAMP_TICKS=T (<= 256): after the single steps, one pgtg_step_many call of 1 + T ticks, whose last launch is
 k_envq<BIG, true> with T ticks (given T <= the handle's ticks per launch), then the tick dimension: every
