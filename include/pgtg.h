@@ -187,7 +187,18 @@ typedef struct pgtg_handle pgtg_handle;
 
 int pgtg_create(const PgtgConfig* cfg, uint64_t n_envs, int32_t device, pgtg_handle** out);
 int pgtg_destroy(pgtg_handle* h);
-/* Queue work on this stream (hipStream_t); NULL = the null stream. */
+/* Queue work on this stream (hipStream_t); NULL = the null stream.  The stream contract of the library:
+ *   - every launch, copy and memset of an entry point goes to the stream bound when it is called, and when the
+ *     entry point returns, everything it wrote to the handle's device state is ordered before the next launch
+ *     on that stream (the allocations of pgtg_create are zeroed before it returns);
+ *   - the handle does not order one stream with another: a caller that binds another stream orders it with the
+ *     work queued on the last one (an event, a synchronisation), as it would for any buffer it moves between
+ *     streams; the same holds for the buffers it binds or passes in;
+ *   - the entry points that read or write device state from the host (the getters, pgtg_set_agent,
+ *     pgtg_add_car, pgtg_set_to_state, pgtg_set_rules, pgtg_dump_state, pgtg_load_state,
+ *     pgtg_set_block_shares with counts) first drain the bound stream themselves;
+ *   - a host array passed in (seeds_host, a state blob, rules, cars, counts) is read before the call returns
+ *     and may be reused or freed at once. */
 int pgtg_set_stream(pgtg_handle* h, void* stream);
 /* Bind the output buffers.  Between step launches the bound `obs` buffer belongs to the handle: the persistent
  * map-queue step kernel (k_envq) writes only the observations that changed since the last launch (whole
@@ -199,7 +210,10 @@ int pgtg_set_stream(pgtg_handle* h, void* stream);
  * correct observations without pgtg_observe.  final_obs and every other output are written in full. */
 int pgtg_set_outputs(pgtg_handle* h, const PgtgOutputs* out);
 /* Seeded reset of env i with seeds_host[i] (NULL: seed_base + global index), only where
- * mask_dev[i] != 0 (NULL: all).  Writes the reset observation to the bound outputs. */
+ * mask_dev[i] != 0 (NULL: all).  Writes the reset observation to the bound outputs.  seeds_host ([N], pageable
+ * or pinned) is copied into a pinned array of the handle before the call returns and uploaded from there on the
+ * handle's stream: the caller's array is not read afterwards.  The call does not wait for the device, except
+ * that a second seed-list reset waits for the first one's upload before it reuses the pinned array. */
 int pgtg_reset(pgtg_handle* h, const uint64_t* seeds_host, uint64_t seed_base, const uint8_t* mask_dev);
 /* Unseeded reset (next spawn block of each env's seed sequence) where mask_dev[i] != 0. */
 int pgtg_reset_unseeded(pgtg_handle* h, const uint8_t* mask_dev);

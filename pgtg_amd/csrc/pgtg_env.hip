@@ -4911,6 +4911,8 @@ struct pgtg_handle {
   std::string err;
   uint64_t seed_offset = 0;  // global index of env 0 (for sharded runs)
   uint64_t* seed_stage = nullptr;  // a masked reset's seed list on the device (allocated at the first one)
+  uint64_t* seed_host = nullptr;   // pinned copy of a reset's seed list (allocated at the first one): the caller's
+  hipEvent_t seed_done = nullptr;  // array is free at return; recorded behind the upload that reads seed_host
   int tune_epb = 0, tune_obs_sub = 0, tune_kt_grid = 0, tune_kt_cap = 0, tune_kt_wpc = 0;  // PgtgConfig.tune_*
   int timing = 0;             // bracket every `timing`-th step launch with an event pair (0: off)
   uint64_t step_launches = 0;
@@ -5046,7 +5048,8 @@ static int dalloc(pgtg_handle* h, T** p, size_t count) {
   void* q = nullptr;
   if (count == 0) count = 1;
   HIPCHK(h, hipMalloc(&q, count * sizeof(T)));
-  HIPCHK(h, hipMemset(q, 0, count * sizeof(T)));
+  // (on the handle's stream, the null stream during create: the next launch on it comes after the zeroes)
+  HIPCHK(h, hipMemsetAsync(q, 0, count * sizeof(T), h->stream));
   h->allocs.push_back(q);
   *p = reinterpret_cast<T*>(q);
   return 0;
@@ -5088,7 +5091,7 @@ static int equal_shares(pgtg_handle* h) {
   std::vector<uint32_t> c(h->q_grid);
   for (uint64_t w = 0; w < h->q_grid; w++) c[w] = (uint32_t)(blocks / h->q_grid + (w < blocks % h->q_grid ? 1 : 0));
   if (int rc = upload_shares(h, c.data())) return rc;
-  HIPCHK(h, hipMemset(h->own_est, 0, (h->q_grid + 1) * sizeof(uint32_t)));
+  HIPCHK(h, hipMemsetAsync(h->own_est, 0, (h->q_grid + 1) * sizeof(uint32_t), h->stream));  // (ordered with k_shares)
   return 0;
 }
 
@@ -5701,6 +5704,8 @@ static int create(pgtg_handle* h, const PgtgConfig* cfg) {
     if (int rc = dalloc(h, &h->own_rem, h->q_grid)) return rc;
     if (int rc = equal_shares(h)) return rc;
   }
+  // every allocation above was zeroed on the null stream, which a non-blocking stream bound later does not wait for
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return PGTG_OK;
 }
 
@@ -5723,6 +5728,8 @@ int pgtg_destroy(pgtg_handle* h) {
   if (!h) return PGTG_OK;
   for (void* p : h->allocs) (void)hipFree(p);
   for (auto e : h->evpool) (void)hipEventDestroy(e);
+  if (h->seed_done) (void)hipEventDestroy(h->seed_done);
+  if (h->seed_host) (void)hipHostFree(h->seed_host);
   delete h;
   return PGTG_OK;
 }
@@ -5912,17 +5919,36 @@ static int queue_fill(pgtg_handle* h) {
   return PGTG_OK;
 }
 
+// The caller's seed list copied into the handle's pinned array and uploaded from there on the handle's stream:
+// the caller's array is not read after this returns.  An upload of an earlier reset still under way is waited for
+// before its source is overwritten (seed_done).
+static int upload_seeds(pgtg_handle* h, uint64_t* dst_dev, const uint64_t* seeds_host) {
+  const size_t bytes = h->n * sizeof(uint64_t);
+  if (!h->seed_host) {
+    void* p = nullptr;
+    HIPCHK(h, hipHostMalloc(&p, bytes ? bytes : 8, hipHostMallocDefault));
+    h->seed_host = static_cast<uint64_t*>(p);
+    HIPCHK(h, hipEventCreateWithFlags(&h->seed_done, hipEventDisableTiming));
+  } else {
+    HIPCHK(h, hipEventSynchronize(h->seed_done));
+  }
+  memcpy(h->seed_host, seeds_host, bytes);
+  HIPCHK(h, hipMemcpyAsync(dst_dev, h->seed_host, bytes, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipEventRecord(h->seed_done, h->stream));
+  return PGTG_OK;
+}
+
 int pgtg_reset(pgtg_handle* h, const uint64_t* seeds_host, uint64_t seed_base, const uint8_t* mask_dev) {
   if (!h) return PGTG_E_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
   if (seeds_host && !mask_dev) {
-    HIPCHK(h, hipMemcpyAsync(h->S.seed, seeds_host, h->n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    if (int rc = upload_seeds(h, h->S.seed, seeds_host)) return rc;
   } else {
     const uint64_t* src = nullptr;
     if (seeds_host) {  // a masked reset with a seed list: staged, then copied for the masked envs
       if (!h->seed_stage)
         if (int rc = dalloc(h, &h->seed_stage, h->n)) return rc;
-      HIPCHK(h, hipMemcpyAsync(h->seed_stage, seeds_host, h->n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+      if (int rc = upload_seeds(h, h->seed_stage, seeds_host)) return rc;
       src = h->seed_stage;
     }
     hipLaunchKernelGGL(k_fill_seeds, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->S.seed, h->n,
@@ -6445,10 +6471,12 @@ int pgtg_load_state(pgtg_handle* h, const void* buf, uint64_t bytes) {
     HIPCHK(h, hipMemcpy(s.ptr, p + off, s.bytes, hipMemcpyHostToDevice));
     off += s.bytes;
   }
-  if (h->S.tr_count) HIPCHK(h, hipMemset(h->S.tr_count, 0, 2 * sizeof(uint32_t)));
-  if (h->S.qctr) HIPCHK(h, hipMemset(h->S.qctr, 0, kQctrWords * sizeof(uint32_t)));  // (dumped with full rings)
+  // (on the handle's stream, as every launch that reads them: the copies above were blocking, these are not)
+  if (h->S.tr_count) HIPCHK(h, hipMemsetAsync(h->S.tr_count, 0, 2 * sizeof(uint32_t), h->stream));
+  if (h->S.qctr) HIPCHK(h, hipMemsetAsync(h->S.qctr, 0, kQctrWords * sizeof(uint32_t), h->stream));  // (dumped with full rings)
   // (a drain's maps not yet counted served requests that a launch per tick drops here)
-  if (h->q_drained) HIPCHK(h, hipMemset(h->own_clk, 0, kWgWords * h->own_grid * sizeof(unsigned long long)));
+  if (h->q_drained)
+    HIPCHK(h, hipMemsetAsync(h->own_clk, 0, kWgWords * h->own_grid * sizeof(unsigned long long), h->stream));
   h->q_drained = false;
   if (h->ep.ret) {  // the episode accumulators are not in the blob: every env starts a new count
     HIPCHK(h, hipMemsetAsync(h->ep.ret, 0, h->n * sizeof(float), h->stream));  // (ordered with k_episode)

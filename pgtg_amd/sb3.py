@@ -223,6 +223,7 @@ class PGTGSB3VecEnv:
             # step); an action outside Discrete(9) is recorded by the kernel per env (error_count())
             a = actions.reshape(self.num_envs)
             if a.dtype != torch.uint8:  # every value outside Discrete(9) becomes the invalid code 255
+                a = a.to(torch.int64)  # (255 does not fit int8; the mapping of Rollout.step)
                 a = torch.where((a < 0) | (a > 8), torch.full_like(a, 255), a).to(torch.uint8)
             self._actions = a
             return

@@ -267,3 +267,35 @@ def test_sb3_device_actions_out_of_range_are_recorded():
     env.step(torch.full((8,), 4, dtype=torch.int64, device="cuda"))
     assert env.venv.error_count()[0] == 0
     env.close()
+
+
+@pytest.mark.parametrize("dtype", [torch.int8, torch.int16, torch.int32, torch.int64])
+def test_sb3_device_actions_of_every_int_dtype_step_as_uint8(dtype):
+    """Device actions of a signed integer dtype step exactly as their uint8 form (int8 once raised: 255 does
+    not fit it), and -1 and 9 are counted as invalid per env, never mapped onto a valid action."""
+    from pgtg_amd import _abi
+    from pgtg_amd.sb3 import PGTGSB3VecEnv
+    N = 8
+    kw = dict(max_episode_steps=5, seed=1, device_obs=True, random_map_width=3, random_map_height=3)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        ref, env = PGTGSB3VecEnv(N, **kw), PGTGSB3VecEnv(N, **kw)
+    assert torch.equal(ref.reset(), env.reset())
+    g = torch.Generator().manual_seed(2)
+    for t in range(6):
+        a = torch.randint(0, 9, (N,), generator=g)
+        bad = {3: -1, 5: 9} if t == 2 else {}
+        u8 = a.clone()
+        for i, v in bad.items():
+            a[i], u8[i] = v, 255
+        want = ref.step(u8.to(torch.uint8).cuda())
+        got = env.step(a.to(dtype).cuda())
+        for w, x in zip(want[:3], got[:3]):
+            assert torch.equal(w, x), t
+        done = want[2]
+        assert torch.equal(want[3].terminal_observation[done], got[3].terminal_observation[done]), t
+        n, code = env.venv.error_count()
+        assert (n, code) == ((2, _abi.PGTG_E_INVALID) if bad else (0, 0)), t
+        assert ref.venv.error_count() == (n, code), t
+    ref.close()
+    env.close()
